@@ -20,7 +20,15 @@ step on the gloo backend: the launch / barrier / MAX-over-ranks / one-line proto
 gradients go through ``shard.GradBucket`` (one 4.04 MB fp32 all-reduce over RCCL/xGMI per step, inside the graph: the
 reference's DDP semantics, train_mvs4.py:389-392).  value = samples/s over all ranks.
 
-Extra objects in the line:
+A plain run does what `value` needs and nothing more: set up, warm up, time EXACTLY ``--steps`` steps in one window
+(``ms_per_step`` = that window / steps), write the outputs if ``--dump-outputs DIR`` is given, print the line.
+``--dump-outputs DIR``: after the timed steps, the arrays the timed path handed out in its last step (every distinct
+tensor of the output dict, ``stageN_<key>``) as ``DIR/<name>.npy`` in float32 (float64 kept), 64 MB at most; the inputs are
+seeded, so two builds can be compared output for output.
+
+``--full`` adds everything else: the timed region as the median of >= 3 windows of ``--steps`` steps, the per-rank window
+and kernel-fingerprint check, and the extra objects below.
+Extra objects in the line (``--full``):
   roofline      the dominant kernel instance of the forward, timed with HIP events on the launch
                 stream in an instrumented eager pass inside this script (same inputs, same kernels)
   rooflines     the same for the dominant convolution kernel AND the fused warp/aggregation kernel of each of
@@ -50,6 +58,48 @@ SHIPPED = dict(arch_mode="fpn", reg_net="reg2d", num_stage=4, fpn_base_channel=8
                group_cor_dim=[8, 8, 4, 4], inverse_depth=True, mono=True, attn_temp=2, attn_fuse_d=True)
 FP32_MFMA_PEAK_TFLOPS = 157.3     # /opt/skills/guides/MI355X_MICROARCH.md: peak FP32 (matrix), dense
 HBM_PEAK_GBS = 8000.0             # same guide: HBM3E peak
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BUDGET_BYTES):
+    """``outputs`` (a tensor, or a dict of tensors / dicts of tensors: what the timed path returns) as ``out_dir/<name>.npy``.
+    Every distinct tensor once (the flattened last-stage entries of MVS4net's dict are stage4's tensors), float32 unless
+    it is float64.  Above ``budget`` in all, every array larger than an equal share of it is replaced by a fixed sample of
+    its flattened elements (seeded, the same indices from run to run).  -> {name: shape written}."""
+    if torch.is_tensor(outputs):
+        outputs = {"output": outputs}
+    arrays, seen = {}, set()
+    for k, v in outputs.items():
+        for k2, t in (v.items() if isinstance(v, dict) else [(None, v)]):
+            if not torch.is_tensor(t):
+                continue
+            key = (t.device, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype)
+            if key in seen:
+                continue
+            seen.add(key)
+            a = t.detach().cpu().numpy()
+            arrays[str(k) if k2 is None else "%s_%s" % (k, k2)] = a if a.dtype == np.float64 else a.astype(np.float32)
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        share = budget // max(1, len(arrays))
+        for name, a in arrays.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def cpu_allowance():
+    """The cores this process may use: its affinity mask, capped by OMP_NUM_THREADS when the environment sets it (a
+    shared host's allowance; os.cpu_count() counts the whole machine)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
 
 
 def load_weights():
@@ -231,7 +281,7 @@ def cpu_baseline(H, W, N, seed):
     import torch.multiprocessing as mp
     from mvster_amd.synthetic import make_inputs
     from oracle import mvs4_oracle as O
-    cores = os.cpu_count() or 1
+    cores = cpu_allowance()
     oracle = O.OracleMVS4net(**SHIPPED)
     oracle.load_state_dict(load_weights(), strict=True)
     oracle.eval()
@@ -302,20 +352,21 @@ def cpu_baseline(H, W, N, seed):
     return {"value": round(total / span, 4), "unit": "depth-maps/s", "cores": nproc * threads, "kind": "port",
             "processes": nproc, "threads_per_process": threads, **out_failed,
             "sample": "%d forwards of the same %dx%d %d-view 4-stage workload by %d independent oracle processes x %d "
-                      "intra-op threads over %.1f s on a %d-thread host" % (total, H, W, N, nproc, threads, span, cores),
+                      "intra-op threads over %.1f s on %d host threads" % (total, H, W, N, nproc, threads, span, cores),
             "single_process": {"value": round(single, 4), "cores": best_t,
                                "sweep_s_per_forward": {str(k): round(v, 3) for k, v in sorted(sweep.items())}}}
 
 
-def timed_windows(step, steps, shard, min_total_s=0.5, max_windows=41, sync=None):
+def timed_windows(step, steps, shard, min_total_s=0.5, max_windows=41, sync=None, windows=None):
     """The contract's timed region -- EXACTLY ``steps`` steps between barrier + synchronise pairs, MAX over ranks -- run as
     k >= 3 back-to-back windows (k odd, chosen from the first window so that the windows add up to >= ``min_total_s``; the
     reduced time is the same on every rank, so every rank picks the same k) and reported through the MEDIAN window: a
     20-step window of this workload is 20 ms, too short for one sample to be robust against a box's clock ramp.
-    -> (median elapsed, every window's elapsed, every window's (min, max) rank-local elapsed)."""
+    ``windows``: exactly that many windows instead (a plain run: 1, i.e. exactly ``steps`` timed steps).
+    -> (median elapsed, every window's elapsed, the reported window's (min, max, this rank's own) rank-local elapsed)."""
     sync = sync or torch.cuda.synchronize
     out, spread = [], []
-    k = 3
+    k = windows or 3
     i = 0
     while i < k:
         sync()
@@ -330,8 +381,8 @@ def timed_windows(step, steps, shard, min_total_s=0.5, max_windows=41, sync=None
         sync()
         el = shard.max_over_ranks(time.perf_counter() - t0)
         out.append(el)
-        spread.append((-shard.max_over_ranks(-mine), shard.max_over_ranks(mine)))
-        if i == 0:
+        spread.append((-shard.max_over_ranks(-mine), shard.max_over_ranks(mine), mine))
+        if i == 0 and not windows:
             k = int(min(max_windows, max(3, -(-1.1 * min_total_s // max(el, 1e-6)))))       # (10 % margin: the first window is the slowest)
             k += 1 - k % 2
         i += 1
@@ -452,8 +503,12 @@ def stub_main(args):
     rank, local_rank, world = shard.init_distributed(backend="gloo")
     if world != args.gpus:
         raise SystemExit("bench.py --gpus %d: launched with WORLD_SIZE=%d" % (args.gpus, world))
-    x = torch.randn(64, 64)
-    step = lambda: (x @ x).sum().item()     # noqa: E731
+    x = torch.randn(64, 64, generator=torch.Generator().manual_seed(0))
+    last = [None]
+
+    def step():
+        last[0] = x @ x
+        return last[0].sum().item()
     if args.mode == "train":
         # the training protocol on a toy module: backward, ONE bucketed all-reduce (shard.GradBucket), SGD update
         torch.manual_seed(0)
@@ -464,24 +519,32 @@ def stub_main(args):
 
         def step():
             opt.zero_grad(set_to_none=True)
-            net(xb).square().mean().backward()
+            last[0] = net(xb).square().mean()
+            last[0].backward()
             bucket.sync()
             opt.step()
     for _ in range(args.warmup):
         step()
-    elapsed, windows, rank_span = timed_windows(step, args.steps, shard, min_total_s=0.02, sync=lambda: None)
+    elapsed, windows, rank_span = timed_windows(step, args.steps, shard, min_total_s=0.02, sync=lambda: None,
+                                                windows=None if args.full else 1)
     ranks_seen = int(round(shard.sum_over_ranks(1.0)))
     if ranks_seen != world:
         raise SystemExit("bench.py: %d ranks answered the collective, WORLD_SIZE=%d" % (ranks_seen, world))
-    # (same reporting as the GPU line: every rank's own rate in rank order, one kernel fingerprint on all ranks)
-    r0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    per_rank = shard.gather_over_ranks(args.steps / max(time.perf_counter() - r0, 1e-9))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last[0], args.dump_outputs)
+    # (same reporting as the GPU line: every rank's own rate in rank order; --full: over one more window, and one kernel
+    # fingerprint on all ranks)
+    if args.full:
+        r0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        per_rank = shard.gather_over_ranks(args.steps / max(time.perf_counter() - r0, 1e-9))
+        hashes = shard.gather_over_ranks(float(int(kernel_source_hash()[:12], 16)))
+        if len(set(hashes)) != 1:
+            raise SystemExit("bench.py: the ranks run different kernel sources")
+    else:
+        per_rank = shard.gather_over_ranks(args.steps / max(rank_span[2], 1e-9))
     rank_ids = shard.gather_over_ranks(float(rank))
-    hashes = shard.gather_over_ranks(float(int(kernel_source_hash()[:12], 16)))
-    if len(set(hashes)) != 1:
-        raise SystemExit("bench.py: the ranks run different kernel sources")
     spread = None
     if args.mode == "train":
         # after the same number of averaged updates every rank holds the same parameters (collectives: every rank calls)
@@ -555,7 +618,8 @@ def train_main(args):
 
 
 def train_measure(args, rank, local_rank, world, steps, warmup, min_total_s=0.5):
-    """One rank's share of the training measurement; rank 0 gets the line (a dict), the others None."""
+    """One rank's share of the training measurement; rank 0 gets the line (a dict), the others None.  Without ``args.full``
+    one window of exactly ``steps`` steps and no instrumented pass."""
     from mvster_amd import MVS4net, MVS4net_loss, shard
     from mvster_amd.graph import GraphedTrainStep
     from mvster_amd.synthetic import make_inputs
@@ -625,22 +689,28 @@ def train_measure(args, rank, local_rank, world, steps, warmup, min_total_s=0.5)
 
     def timed_step():
         last[0] = step()
-    elapsed, windows, rank_span = timed_windows(timed_step, steps, shard, min_total_s=min_total_s, max_windows=9)
+    elapsed, windows, rank_span = timed_windows(timed_step, steps, shard, min_total_s=min_total_s, max_windows=9,
+                                                windows=None if args.full else 1)
     loss = last[0]
     ranks_seen = int(round(shard.sum_over_ranks(1.0)))
     if ranks_seen != world:
         raise SystemExit("bench.py: %d ranks answered the collective, WORLD_SIZE=%d" % (ranks_seen, world))
-    per_rank = shard.gather_over_ranks(steps * B / max(rank_span[1] if world == 1 else rank_local_s(timed_step, steps), 1e-9))
-    hashes = shard.gather_over_ranks(float(int(kernel_source_hash()[:12], 16)))
-    if len(set(hashes)) != 1:
-        raise SystemExit("bench.py: the ranks run different kernel sources")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs({"loss": loss}, args.dump_outputs)
+    if args.full:
+        per_rank = shard.gather_over_ranks(steps * B / max(rank_span[1] if world == 1 else rank_local_s(timed_step, steps), 1e-9))
+        hashes = shard.gather_over_ranks(float(int(kernel_source_hash()[:12], 16)))
+        if len(set(hashes)) != 1:
+            raise SystemExit("bench.py: the ranks run different kernel sources")
+    else:
+        per_rank = shard.gather_over_ranks(steps * B / max(rank_span[2], 1e-9))
     last_loss = float(loss.item())
     # every rank must hold the same parameters after the same averaged updates (collectives: every rank calls)
     digest = float(sum(p.detach().double().sum() for p in params))
     spread = shard.max_over_ranks(digest) + shard.max_over_ranks(-digest)
 
     rooflines = []
-    if rank == 0:
+    if rank == 0 and args.full:
         timer = TrainKernelTimer()
         timer.install()
         try:
@@ -704,6 +774,11 @@ def main():
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--views", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: median of >= 3 timed windows, per-rank window and fingerprint check, "
+                         "rooflines, CPU baseline, the PCIe-inclusive, API-call, batched, larger-workload and training figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of hipGraph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel table to stderr")
@@ -800,20 +875,25 @@ def main():
     imgs, proj, dv = make_inputs(nviews=args.views, H=args.height, W=args.width, seed=units[0], device=dev, batch=args.batch)
 
     sequential = None
+    last = [None]                              # what the last step handed out (--dump-outputs)
     if args.no_graph:
-        step = lambda: model.forward_eager(imgs, proj, dv)   # noqa: E731
+        def step():
+            last[0] = model.forward_eager(imgs, proj, dv)
     elif args.inflight <= 1:
         graphed = GraphedForward(model, imgs, proj, dv)
-        step = lambda: graphed()               # noqa: E731
+
+        def step():
+            last[0] = graphed()
     else:
-        # reference point: one depth map at a time (latency of a single forward)
-        g1 = GraphedForward(model, imgs, proj, dv)
-        for _ in range(args.warmup):
-            g1()
-        nseq = max(10, min(args.steps, 50))
-        seq_el, seq_windows, _ = timed_windows(lambda: g1(), nseq, shard, min_total_s=0.25)
-        sequential = seq_el / nseq
-        del g1
+        if args.full:
+            # reference point: one depth map at a time (latency of a single forward)
+            g1 = GraphedForward(model, imgs, proj, dv)
+            for _ in range(args.warmup):
+                g1()
+            nseq = max(10, min(args.steps, 50))
+            seq_el, seq_windows, _ = timed_windows(lambda: g1(), nseq, shard, min_total_s=0.25)
+            sequential = seq_el / nseq
+            del g1
         # several independent depth maps in flight: one captured forward + one stream per slot
         slots = []
         for k in range(args.inflight):
@@ -828,31 +908,38 @@ def main():
             st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 g.graph.replay()
+            last[0] = g.outputs
 
     for _ in range(args.warmup):
         step()
-    elapsed, windows, rank_span = timed_windows(step, args.steps, shard)
+    elapsed, windows, rank_span = timed_windows(step, args.steps, shard, windows=None if args.full else 1)
     ranks_seen = int(round(shard.sum_over_ranks(1.0)))
     if ranks_seen != world:
         raise SystemExit("bench.py: %d ranks answered the collective, WORLD_SIZE=%d" % (ranks_seen, world))
-    # every rank's own rate over one more window of the same loop (no MAX over ranks in it): a straggler GPU shows here;
-    # and every rank must run the same kernels (fingerprint of the sources the in-tree library was built from)
-    torch.cuda.synchronize()
-    shard.barrier()
-    r0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    per_rank = shard.gather_over_ranks(args.steps * args.batch / (time.perf_counter() - r0))
-    hashes = shard.gather_over_ranks(float(int(kernel_source_hash()[:12], 16)))
-    if len(set(hashes)) != 1:
-        raise SystemExit("bench.py: the ranks run different kernel sources (%s)" % sorted(set(hashes)))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last[0], args.dump_outputs)       # (timed_windows ended with a device synchronisation)
+    if args.full:
+        # every rank's own rate over one more window of the same loop (no MAX over ranks in it): a straggler GPU shows here;
+        # and every rank must run the same kernels (fingerprint of the sources the in-tree library was built from)
+        torch.cuda.synchronize()
+        shard.barrier()
+        r0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        per_rank = shard.gather_over_ranks(args.steps * args.batch / (time.perf_counter() - r0))
+        hashes = shard.gather_over_ranks(float(int(kernel_source_hash()[:12], 16)))
+        if len(set(hashes)) != 1:
+            raise SystemExit("bench.py: the ranks run different kernel sources (%s)" % sorted(set(hashes)))
+    else:
+        # every rank's own time of the timed window itself
+        per_rank = shard.gather_over_ranks(args.steps * args.batch / rank_span[2])
 
     # ---- the same loop with the inputs coming from the host: pinned buffers, one copy stream -----------------------
     # (the reference's loop moves every sample to the GPU first, test_mvs4.py:202-207).  `value` above keeps the inputs
     # resident in HBM as the metric is defined; this is the PCIe-inclusive rate measured, not computed.
     with_h2d = None
-    if not args.no_graph and args.inflight > 1 and not args.no_stream_inputs:
+    if args.full and not args.no_graph and args.inflight > 1 and not args.no_stream_inputs:
         from mvster_amd.graph import pack_sample
         copy_stream = torch.cuda.Stream(device=dev)
         # One packed pinned buffer per sample and ONE copy per depth map (GraphedForward(packed=True): the static inputs are
@@ -943,14 +1030,14 @@ def main():
     #  runtime's copy path in a state that slows a later pinned pipeline by 20 % -- 758 against 948 depth-maps/s, same box,
     #  alternating runs, gpurun_out/r5q -- while this leg measures the same after it as before it)
     api_call = None
-    if rank == 0 and world == 1 and not args.no_graph and not args.no_api_call:      # (N = 1 only: its windows use the barrier / MAX protocol)
+    if args.full and rank == 0 and world == 1 and not args.no_graph and not args.no_api_call:      # (N = 1 only: its windows use the barrier / MAX protocol)
         api_call = api_call_measure(args, model, dev, units[0], shard)
 
     # ---- the same workload with several depth maps per forward call (the B of MVS4net.forward; the reference's eval driver
     # uses 1, its training 2): not the headline -- `value` stays one depth map per call, comparable with every earlier record --
     # but what a throughput-oriented caller gets: the coarse stages' short launches are shared by the maps of a batch.
     batched = []
-    if (rank == 0 and world == 1 and not args.no_graph and args.inflight > 1 and not args.no_batched and args.batch == 1
+    if (args.full and rank == 0 and world == 1 and not args.no_graph and args.inflight > 1 and not args.no_batched and args.batch == 1
             and (args.height, args.width, args.views) == (512, 640, 5)):
         for bsz in (2, 4):
             try:
@@ -981,7 +1068,7 @@ def main():
 
     # ---- the other inference configurations of BASELINE.json (runnable forms of configs[2] and configs[4]) ----------
     other_configs = []
-    if rank == 0 and not args.no_graph and not args.no_other_configs and (args.height, args.width, args.views) == (512, 640, 5):
+    if args.full and rank == 0 and not args.no_graph and not args.no_other_configs and (args.height, args.width, args.views) == (512, 640, 5):
         # (published: the reference's README.md:74-75, one RTX 3090, timer without a device synchronisation; "mid" is 832x1152
         #  as test_mvs4.py:41-42 + the /64 rounding of general_eval4.py:92-100 run it, "raw" is 1152x1600)
         for (oh, ow, on, label, pub) in ((832, 1152, 5, "DTU mid as the reference's test script runs it (832x1152, 5 views)", 0.09),
@@ -1018,7 +1105,7 @@ def main():
     rooflines = []
     rooflines_coherent = None
     table = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.kernel_table):
         timer = KernelTimer()
         timer.install()
         overlap = model.overlap_streams
@@ -1115,7 +1202,7 @@ def main():
         # the same warp launches in the geometrically coherent regime (prob heads zeroed: every pixel keeps hypothesis 0,
         # so the depth maps handed from stage to stage are smooth, as for a trained network; the fixture's random weights
         # make neighbouring pixels pick unrelated hypotheses)
-        if not args.no_coherent:
+        if args.full and not args.no_coherent:
             smooth = MVS4net(**SHIPPED)
             smooth.load_state_dict(model.state_dict(), strict=True)
             with torch.no_grad():
@@ -1148,12 +1235,12 @@ def main():
 
     # ---- BASELINE.json configs[3] on this rank: a few captured training steps (N = 1 only; `--mode train` is the full line) ---
     train = None
-    if world == 1 and not args.no_train and not args.no_graph and (args.height, args.width, args.views, args.batch) == (512, 640, 5, 1):
+    if args.full and world == 1 and not args.no_train and not args.no_graph and (args.height, args.width, args.views, args.batch) == (512, 640, 5, 1):
         try:
             slots = graphed = step = None         # the eval graphs' memory goes back to the allocator first
             torch.cuda.empty_cache()
             targs = argparse.Namespace(**vars(args))
-            targs.batch, targs.coherent = 2, False
+            targs.batch, targs.coherent, targs.dump_outputs = 2, False, None
             tl = train_measure(targs, rank, local_rank, world, steps=10, warmup=3, min_total_s=0.3)
             train = {k: tl[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype", "timing", "loss_last")}
             train["config"] = tl["config"]
@@ -1164,7 +1251,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores, bounded sample ----------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.height, args.width, args.views, units[0])
 
     if rank == 0:

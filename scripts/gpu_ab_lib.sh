@@ -11,10 +11,10 @@ fi
 for rep in 1 2 3; do
 for lib in tree other; do
   if [ $lib = other ]; then export MVSTER_LIB=$OTHER MVSTER_LIB_LAX=1; else unset MVSTER_LIB MVSTER_LIB_LAX; fi
-  timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs --no-stream-inputs --no-coherent --no-train 2>/dev/null > gpurun_out/ab_$lib.json
+  timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs --no-stream-inputs --no-coherent --no-train 2>/dev/null > "$TMPDIR/ab_$lib.json"
   python - <<PY
 import json
-d=json.loads(open('gpurun_out/ab_$lib.json').read().strip().splitlines()[-1])
+d=json.loads(open('$TMPDIR/ab_$lib.json').read().strip().splitlines()[-1])
 print('$lib', {k:d.get(k) for k in ('value','ms_per_step','single_forward_ms')})
 PY
 done

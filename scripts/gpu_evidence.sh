@@ -14,14 +14,14 @@ cp gpurun_out/pmc/pmc_traffic.json profiles/pmc_traffic.json
 cp gpurun_out/pmc/pmc_traffic.json $E/pmc_traffic.json
 cp gpurun_out/pmc/summary.txt $E/${TAG}_pmc_summary.txt
 cp gpurun_out/pmc/pmc_per_kernel.json $E/${TAG}_pmc_per_kernel.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --kernel-table > $E/${TAG}_bench_driver_args.json 2> $E/${TAG}_kernel_table_hip_events.txt; echo "bench (driver arguments) exit $?"; cut -c1-260 $E/${TAG}_bench_driver_args.json
-timeout 900 python bench.py --no-cpu-baseline --no-train --no-other-configs > $E/${TAG}_bench_200steps.json 2>/dev/null; cut -c1-200 $E/${TAG}_bench_200steps.json
-bash scripts/gpu_profile.sh > $E/profile_run.txt 2>&1; tail -3 $E/profile_run.txt
-cp $(find gpurun_out/prof -name "*kernel_stats.csv" | head -1) $E/${TAG}_rocprof_kernel_stats.csv
-cp gpurun_out/prof/bench_under_rocprof.json $E/${TAG}_bench_under_rocprof.json
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --kernel-table > $E/${TAG}_bench_driver_args.json 2> $E/${TAG}_kernel_table_hip_events.txt; echo "bench (driver arguments) exit $?"; cut -c1-260 $E/${TAG}_bench_driver_args.json
+timeout 900 python bench.py --full --no-cpu-baseline --no-train --no-other-configs > $E/${TAG}_bench_200steps.json 2>/dev/null; cut -c1-200 $E/${TAG}_bench_200steps.json
+PROF_DIR=$PWD/$E/prof bash scripts/gpu_profile.sh > $E/profile_run.txt 2>&1; tail -3 $E/profile_run.txt
+cp $(find $E/prof -name "*kernel_stats.csv" | head -1) $E/${TAG}_rocprof_kernel_stats.csv
+cp $E/prof/bench_under_rocprof.json $E/${TAG}_bench_under_rocprof.json
 python scripts/layer_table.py 2>&1 | grep -v amdgpu.ids > $E/${TAG}_layer_table.txt; tail -1 $E/${TAG}_layer_table.txt
-timeout 600 python bench.py --mode train --steps 20 --warmup 3 2>/dev/null > $E/${TAG}_train_bench.json; cut -c1-200 $E/${TAG}_train_bench.json
-timeout 600 python bench.py --mode train --steps 20 --warmup 3 --coherent 2>/dev/null > $E/${TAG}_train_bench_smooth_depth.json; cut -c1-200 $E/${TAG}_train_bench_smooth_depth.json
+timeout 600 python bench.py --full --mode train --steps 20 --warmup 3 2>/dev/null > $E/${TAG}_train_bench.json; cut -c1-200 $E/${TAG}_train_bench.json
+timeout 600 python bench.py --full --mode train --steps 20 --warmup 3 --coherent 2>/dev/null > $E/${TAG}_train_bench_smooth_depth.json; cut -c1-200 $E/${TAG}_train_bench_smooth_depth.json
 # training categories of the CAPTURED step (what the bench replays): 6 replays minus 1, kernel by kernel
 timeout 900 bash scripts/gpu_train_cat.sh evtrain > /dev/null 2>&1
 cp gpurun_out/evtrain/train_kernel_stats.csv $E/${TAG}_train_kernel_stats.csv

@@ -61,8 +61,9 @@ def test_train_mode_under_the_drivers_launcher_two_ranks():
 
 def test_four_ranks_train_protocol():
     """Four gloo ranks through the training protocol (bucketed all-reduce): every rank reports, the windows are timed on all
-    of them (fastest / slowest rank of the reported window in the line), parameters agree afterwards."""
-    line = _run(["--gpus", "4", "--mode", "train"])
+    of them (fastest / slowest rank of the reported window in the line), parameters agree afterwards.  (--full: the median
+    of several windows.)"""
+    line = _run(["--gpus", "4", "--mode", "train", "--full"])
     assert line["n_gpus"] == 4 and line["ranks_seen"] == 4 and abs(line["param_digest_spread"]) <= 1e-9
     assert line["rank_order"] == [0, 1, 2, 3] and len(line["per_rank_value"]) == 4
     t = line["timing"]
@@ -89,3 +90,55 @@ def test_kernel_source_hash_tracks_the_sources(tmp_path):
     import bench
     h = bench.kernel_source_hash()
     assert len(h) == 16 and h == bench.kernel_source_hash()
+
+
+def test_plain_run_times_exactly_steps():
+    """Without --full the timed region is ONE window of exactly --steps steps, and ms_per_step is that window / steps."""
+    for extra in (["--gpus", "1"], ["--gpus", "2", "--mode", "train"]):
+        line = _run(extra)
+        t = line["timing"]
+        assert t["windows"] == 1 and t["steps_per_window"] == 5 and len(t["window_ms"]) == 1
+        assert abs(line["ms_per_step"] * 5 - t["window_ms"][0]) < 1e-2
+        assert len(line["per_rank_value"]) == line["n_gpus"] and min(line["per_rank_value"]) > 0
+
+
+def test_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs DIR: the last timed step's result as .npy, the same from run to run with the same arguments."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        _run(["--gpus", "1", "--dump-outputs", str(d)])
+        runs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert list(runs[0]) == ["output.npy"] and runs[0]["output.npy"].dtype == np.float32
+    assert runs[0]["output.npy"].shape == (64, 64)
+    assert np.array_equal(runs[0]["output.npy"], runs[1]["output.npy"])
+
+
+def test_dump_outputs_layout_and_budget(tmp_path):
+    """Every distinct tensor once (the flattened last-stage entries alias stage4's), float32 unless float64, and above the
+    budget a fixed sample of the large arrays, the same indices every time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    depth = torch.rand(1, 64, 80, generator=g)
+    outs = {"stage1": {"depth": torch.rand(1, 8, 10, generator=g), "attn_weight": torch.rand(1, 8, 8, 10, generator=g)},
+            "stage4": {"depth": depth, "hypo": torch.rand(1, 4, 64, 80, generator=g).double()},
+            "depth": depth, "count": torch.arange(6)}
+    shapes = bench.dump_outputs(outs, str(tmp_path / "all"))
+    assert shapes == {"stage1_depth": [1, 8, 10], "stage1_attn_weight": [1, 8, 8, 10], "stage4_depth": [1, 64, 80],
+                      "stage4_hypo": [1, 4, 64, 80], "count": [6]}
+    assert np.load(tmp_path / "all" / "stage4_hypo.npy").dtype == np.float64
+    assert np.load(tmp_path / "all" / "count.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "all" / "stage4_depth.npy"), depth.numpy())
+    budget = 16 << 10
+    a = bench.dump_outputs(outs, str(tmp_path / "a"), budget=budget)
+    b = bench.dump_outputs(outs, str(tmp_path / "b"), budget=budget)
+    assert a == b and sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) - 128 for n in a) <= budget
+    for n in a:
+        assert np.array_equal(np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy")))
+    full = np.load(tmp_path / "all" / "stage4_hypo.npy").reshape(-1)
+    part = np.load(tmp_path / "a" / "stage4_hypo.npy")
+    assert part.size < full.size and np.isin(part, full).all()
