@@ -449,7 +449,9 @@ int mvster_fine_weights_bwd(const float* wo, const float* wi, const float* bi, c
  * tensor's moments in the flat exp_avg / exp_avg_sq buffers).  step_cells [2] device floats: cell 0 = number of updates
  * done so far, + 1 afterwards (cell 1 scratch); lr = one DEVICE float (a schedule reaches a captured step by rewriting
  * it between replays).  ceil(count / 128) launches (+ 1 when that is odd); the pointers travel as
- * kernel arguments, so a captured step records them with the launch. */
+ * kernel arguments, so a captured step records them with the launch.  Every pointer and size is checked before the first
+ * launch: MVSTER_ERR_NULL (a null params[i] / grads[i]) or MVSTER_ERR_SHAPE (a negative size / offset) leave the tensors, the
+ * moments and the step cells untouched. */
 int mvster_fused_adam(const void* const* params, const void* const* grads, const int* sizes, const int* state_offs, int count,
                       float* exp_avg, float* exp_avg_sq, float* step_cells, const float* lr, double beta1, double beta2,
                       double eps, double weight_decay, void* stream);

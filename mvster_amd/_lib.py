@@ -9,6 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVSTER_LIB") or os.path.join(_HERE, "csrc", "libmvster_hip.so")   # env: A/B builds
 
+ERR_NULL, ERR_SHAPE, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3, -4      # MVSTER_ERR_* of include/mvster_hip.h
 ERRORS = {-1: "NULL pointer", -2: "bad shape", -3: "unsupported channel/tile combination", -4: "kernel launch failed"}
 
 _f = ctypes.c_void_p     # device pointers are passed as integers

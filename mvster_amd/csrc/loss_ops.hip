@@ -15,6 +15,7 @@
 namespace {
 
 constexpr int kMaxIters = 16;
+constexpr float kFastMaxExponent = 60.0f;   // sinkhorn_fast_kernel only while its largest constant exp((D-1) / eps) stays below e^60
 
 // CONT = false: the discrete form (D target bins, one-hot on the hypothesis nearest to the ground truth).
 // CONT = true: the continuous form (ot_continous, models/mvs4net_utils.py:1111-1123): E = D + 1 target columns, all the
@@ -286,12 +287,18 @@ int launch_sinkhorn(const float* attn, const float* hypo, const float* gt, const
     dim3 grid((unsigned)((n + 127) / 128)), block(128);
     const float inv_eps = 1.0f / eps;
     if constexpr (!CONT) {
-        // the shipped stage widths on the factored form (D exponentials per update); others on the general kernel
-#define MV_F(D_) if (D == D_) { hipLaunchKernelGGL((sinkhorn_fast_kernel<D_>), grid, block, 0, s, attn, hypo, gt, loss_pix, jac, B, HW, iters, inv_eps); return mv_check_launch(); }
-        MV_F(4) MV_F(8)
+        // the shipped stage widths on the factored form (D exponentials per update); others on the general kernel.  The
+        // factored form keeps E_k = exp(k / eps) unshifted, up to exp((D-1) / eps): fp32 overflows past exp(88.7), and the
+        // approximate __logf / __expf lose digits on the way there, so it takes only (D-1) / eps < kFastMaxExponent
+        // (eps > 0.117 at D = 8, eps > 0.05 at D = 4); smaller eps goes to the general kernel, which shifts every
+        // exponential by its maximum and holds for any eps
+        if ((float)(D - 1) * inv_eps < kFastMaxExponent) {
+#define MV_F(D_) if (D == D_) { MV_NOTE_KERNEL("sinkhorn_fast_kernel<%d>", D_); hipLaunchKernelGGL((sinkhorn_fast_kernel<D_>), grid, block, 0, s, attn, hypo, gt, loss_pix, jac, B, HW, iters, inv_eps); return mv_check_launch(); }
+            MV_F(4) MV_F(8)
 #undef MV_F
+        }
     }
-#define MV_S(D_) if (D == D_) { hipLaunchKernelGGL((sinkhorn_kernel<D_, CONT>), grid, block, 0, s, attn, hypo, gt, mask, loss_pix, jac, B, HW, iters, inv_eps); return mv_check_launch(); }
+#define MV_S(D_) if (D == D_) { MV_NOTE_KERNEL("sinkhorn_kernel<%d, %s>", D_, CONT ? "true" : "false"); hipLaunchKernelGGL((sinkhorn_kernel<D_, CONT>), grid, block, 0, s, attn, hypo, gt, mask, loss_pix, jac, B, HW, iters, inv_eps); return mv_check_launch(); }
     if (!CONT) { MV_S(2) }
     MV_S(3) MV_S(4) MV_S(5) MV_S(6) MV_S(7) MV_S(8)
     // 9..16 hypotheses (MVS4net accepts stage_splits up to 16): same code; the potentials' history no longer fits the

@@ -427,6 +427,12 @@ extern "C" int mvster_fused_adam(const void* const* params, const void* const* g
                                  double beta2, double eps, double weight_decay, void* stream) {
     if (!params || !grads || !sizes || !state_offs || !exp_avg || !exp_avg_sq || !step_cells || !lr) return MVSTER_ERR_NULL;
     if (count <= 0) return MVSTER_ERR_SHAPE;
+    // every tensor is checked before the first launch: an error returned half-way would leave the tensors of the earlier
+    // launches updated and the step count bumped
+    for (int i = 0; i < count; ++i) {
+        if (!params[i] || !grads[i]) return MVSTER_ERR_NULL;
+        if (sizes[i] < 0 || state_offs[i] < 0) return MVSTER_ERR_SHAPE;
+    }
     hipStream_t s = (hipStream_t)stream;
     const int launches = (count + kAdamMaxTensors - 1) / kAdamMaxTensors;
     // every launch reads `in`, writes `out`; the first one adds 1.  With an even number of launches the count ends in cell 0;
@@ -438,7 +444,6 @@ extern "C" int mvster_fused_adam(const void* const* params, const void* const* g
         a.count = 0;
         int blocks = 0;
         for (int i = l * kAdamMaxTensors; i < count && a.count < kAdamMaxTensors; ++i) {
-            if (!params[i] || !grads[i] || sizes[i] < 0) return MVSTER_ERR_NULL;
             a.t[a.count] = AdamTensor{(float*)params[i], (const float*)grads[i], state_offs[i], sizes[i]};
             a.first_block[a.count] = blocks;
             blocks += (sizes[i] + 1023) / 1024;

@@ -339,6 +339,9 @@ class GraphedTrainStep:
     train_mvs4.py:389-392: averaged gradients, per-rank BatchNorm statistics).  The optimizer must be built with
     ``capturable=True`` (torch.optim.Adam / AdamW); the loss function takes ``(outputs, depth_gt_ms, mask_ms)`` and
     returns the scalar to minimise first, like ``MVS4net_loss``.
+
+    The graph updates the optimizer's state tensors by address: ``optimizer.load_state_dict`` replaces them (and
+    ``optim.FusedAdam``'s flat buffers), so the step must be rebuilt after it -- a replay after it raises.
     """
 
     # HIP streams the postponed weight-gradient kernels are spread over (train_ops.deferred_wgrad_finish).  They are persistent
@@ -401,12 +404,23 @@ class GraphedTrainStep:
         # (with a collective in the step, RCCL's watchdog thread touches the device during the capture: relaxed mode)
         collective = grad_sync is not None and (grad_sync.world() > 1 or grad_sync.always_reduce)
         mode = {"capture_error_mode": "thread_local"} if collective else {}
-        with torch.cuda.graph(self.graph, **mode):
+        # the capture stream: none of the streams the step forks and joins (train_ops.side_stream)
+        from .train_ops import side_stream
+        streams = [s for s in getattr(bare, "_side_streams", {}).values() if isinstance(s, torch.cuda.Stream)]
+        self._capture_stream = side_stream(torch.cuda.current_stream().device, avoid=streams + [side])
+        with torch.cuda.graph(self.graph, stream=self._capture_stream, **mode):
             self.loss = self._step()
+        # (a list, not a method of self: the optimizer's hook must not keep this step alive)
+        self._state_replaced = replaced = [False]
+        self._load_hook = optimizer.register_load_state_dict_post_hook(lambda opt: replaced.__setitem__(0, True))
 
     def close(self):
         """Unregister this step's epoch cell (the model's tensors are then stamped by version / address alone again)."""
         self._cache.cells.drop(self._cell)
+        hook = getattr(self, "_load_hook", None)
+        if hook is not None:
+            hook.remove()
+            self._load_hook = None
 
     def __del__(self):
         try:
@@ -441,6 +455,9 @@ class GraphedTrainStep:
     def __call__(self, imgs=None, proj_matrices=None, depth_values=None, depth_gt_ms=None, mask_ms=None):
         """Copy a new sample (same shapes) into the static buffers and run the captured step; returns the static loss
         tensor (overwritten by the next call)."""
+        if self.graph is not None and self._state_replaced[0]:
+            raise RuntimeError("GraphedTrainStep: optimizer.load_state_dict() replaced the state the captured step updates; "
+                               "build a new GraphedTrainStep")
         if imgs is not None:
             for dst, src in zip(self.imgs, imgs):
                 dst.copy_(src, non_blocking=True)

@@ -39,6 +39,7 @@ def sinkhorn_loss(gt_depth, hypo_depth, attn_weight, mask, iters, eps=1, continu
     """The loss value of ``sinkhorn`` (its second return) on the fused gfx950 kernel (``mvster_sinkhorn`` /
     ``mvster_sinkhorn_continuous``): GPU tensors, D <= 16 hypotheses (what ``MVS4net`` accepts as ``stage_splits``; the shipped 4/8 keep a
     pixel's whole problem in registers, 9..16 spill the iteration history to scratch), iters <= 16.  There is no tensor-level fallback: other inputs raise."""
+    _check_eps(eps, "sinkhorn_loss")
     D = attn_weight.shape[1]
     if not attn_weight.is_cuda:
         raise RuntimeError("mvster_amd.loss.sinkhorn_loss runs on MI355X only (there is no CPU fallback)")
@@ -89,7 +90,14 @@ class _StageLoss(torch.autograd.Function):
         return (g_attn, g_mono, g_total if ctx.needs_input_grad[2] else None) + (None,) * 10
 
 
-def _check_stage(attn_weight, iters, name):
+def _check_eps(eps, name):
+    # (1 / eps scales the kernels' cost: eps <= 0, NaN, or so small that 1 / eps overflows fp32, has no transport plan)
+    if not float(eps) > 1.0 / 3.4e38:
+        raise ValueError("%s: the entropic regularisation eps must be a positive number, got %r" % (name, eps))
+
+
+def _check_stage(attn_weight, iters, name, eps=1.0):
+    _check_eps(eps, name)
     D = attn_weight.shape[1]
     if not attn_weight.is_cuda:
         raise RuntimeError("mvster_amd.loss.%s runs on MI355X only (there is no CPU fallback)" % name)
@@ -102,7 +110,7 @@ def stage_losses(gt_depth, hypo_depth, attn_weight, mask, mono_depth=None, iters
     """(l1, ot, out_of_range_ratio) of one stage, as MVS4net_loss forms them (models/MVS4Net.py:131-151), on the fused
     gfx950 kernels; ``l1`` is 0 when ``mono_depth`` is None.  GPU tensors, 3 <= D <= 16 hypotheses, iters <= 16: there is no
     tensor-level fallback, other inputs raise."""
-    _check_stage(attn_weight, iters, "stage_losses")
+    _check_stage(attn_weight, iters, "stage_losses", eps)
     l1, ot, ratio, _ = _StageLoss.apply(attn_weight, mono_depth, None, hypo_depth, gt_depth, mask, int(iters), float(eps),
                                         bool(continuous), bool(inverse), 1.0, 1.0, 1.0)
     return l1, ot, ratio
@@ -112,7 +120,7 @@ def stage_losses_total(gt_depth, hypo_depth, attn_weight, mask, mono_depth, tota
                        w_stage):
     """``stage_losses`` plus the running total of MVS4net_loss: -> (l1, ot, out_of_range_ratio, total + w_stage * (w_l1 * l1 +
     w_ot * ot)) (models/MVS4Net.py:131-151), ``total`` None for the first stage.  One fused forward, one fused backward."""
-    _check_stage(attn_weight, iters, "MVS4net_loss")
+    _check_stage(attn_weight, iters, "MVS4net_loss", eps)
     return _StageLoss.apply(attn_weight, mono_depth, total, hypo_depth, gt_depth, mask, int(iters), float(eps), bool(continuous),
                             bool(inverse), float(w_l1), float(w_ot), float(w_stage))
 

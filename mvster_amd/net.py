@@ -57,6 +57,13 @@ class _WarpAggPyr(torch.autograd.Function):
     def backward(ctx, grad, grad_ref_maps):
         pyr, rt, hypo, out, wsum = ctx.saved_tensors
         B, G, group_cor, attn_fuse_d, attn_temp = ctx.cfg
+        if pyr.is_cuda:
+            # a cascade stage on a side stream (MVS4net.train_side_stages) reads here a level allocated on the main or the
+            # FPN's tail stream; autograd drops its last reference when this returns, so without this the block would go
+            # back to that stream's pool while the kernels below may still read it (mono=False: nothing else holds the
+            # level).  No-op on the allocating stream; under capture the allocator keeps such a block out of the pool
+            # until the capture ends, i.e. the level stays reserved through the backward's final join.
+            pyr.record_stream(torch.cuda.current_stream(pyr.device))
         if grad is None:
             g_pyr = torch.zeros_like(pyr)
         else:
@@ -442,6 +449,12 @@ class MVS4net(nn.Module):
                 off(False)
             MVS4net._stream_warning_off = True
 
+    def _train_stream(self, dev):
+        """A side stream of the training step: distinct from the current stream, this model's other streams and the
+        weight-gradient streams (train_ops.side_stream)."""
+        from .train_ops import side_stream
+        return side_stream(dev, avoid=[torch.cuda.current_stream(dev)] + list(self._side_streams.values()))
+
     def _forward_train(self, imgs, proj_matrices, depth_values, teacher=None):
         """Differentiable forward with every convolution pass (forward, input and weight gradients) and the
         fused warp/correlation/aggregation on the gfx950 kernels.  The FPN runs once over all views (view-major
@@ -462,7 +475,7 @@ class MVS4net(nn.Module):
         if self.train_fpn_tail_stream and x.is_cuda and isinstance(self.feature, FPN4) and self.num_stage >= 3:
             tail = self._side_streams.get(("fpn_tail", dev))
             if tail is None:
-                tail = self._side_streams[("fpn_tail", dev)] = torch.cuda.Stream(device=dev)
+                tail = self._side_streams[("fpn_tail", dev)] = self._train_stream(dev)
             self._no_stream_warning()
         if isinstance(self.feature, FPN4):
             self.feature.tail_stream = tail
@@ -491,7 +504,7 @@ class MVS4net(nn.Module):
                 key = ("train", dev, s if self.train_side_separate else 0)
                 side = self._side_streams.get(key)
                 if side is None:
-                    side = self._side_streams[key] = torch.cuda.Stream(device=dev)
+                    side = self._side_streams[key] = self._train_stream(dev)
                 side.wait_stream(cur)
             with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
                 with torch.no_grad():

@@ -164,7 +164,7 @@ def warp_agg_fwd_sched_cl(ref_cl, src_cl, rt, G, D, attn_fuse_d=True, attn_temp=
     rc = lib.mvster_warp_agg_fwd_sched(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(inv_min), _ptr(inv_max), _ptr(depth_values),
                                        ndv, _ptr(hypo), _ptr(out), None, B, NV, C, G, D, h, w, Hs, Ws, h * w * C,
                                        B * Hs * Ws * C, Hs * Ws * C, int(attn_fuse_d), float(attn_temp), mode, _stream())
-    if rc == -3:
+    if rc == _lib.ERR_UNSUPPORTED:
         return None
     _lib.check(rc, "warp_agg_fwd_sched")
     return out, hypo
@@ -180,7 +180,7 @@ def warp_agg_bwd_sorted_scratch(B, NV, C, D, h, w, Hs, Ws):
     import ctypes
     nf, ni = ctypes.c_long(0), ctypes.c_long(0)
     rc = _lib.load().mvster_warp_agg_bwd_sorted_scratch(B, NV, C, D, h, w, Hs, Ws, ctypes.addressof(nf), ctypes.addressof(ni))
-    if rc == -3:
+    if rc == _lib.ERR_UNSUPPORTED:
         return None
     _lib.check(rc, "warp_agg_bwd_sorted_scratch")
     return nf.value, ni.value

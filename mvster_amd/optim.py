@@ -8,6 +8,12 @@ The step counter and the learning rate live on the device: a captured step (``gr
 learning-rate schedule reaches it -- ``sync_hyperparameters()`` (called by ``GraphedTrainStep`` before every replay, and by
 ``step()``) rewrites the device cell when ``group["lr"]`` changed.  betas / eps / weight_decay are launch arguments: they are
 frozen into a captured step, as with torch's own optimizers.
+
+One step counter per group: adopting a torch.optim.Adam state whose parameters of one group have different ``step`` counts
+(a parameter without a state counting as step 0) raises at the first ``step()`` (put such parameters into groups of their
+own).  ``load_state_dict`` replaces the flat moment
+buffers and the step cell, which a captured step (``graph.GraphedTrainStep``) has recorded by address: rebuild the captured
+step after it (its replay raises otherwise).
 """
 import ctypes
 
@@ -50,6 +56,17 @@ class FusedAdam(torch.optim.Optimizer):
              "step_cells": torch.zeros(2, device=dev), "lr_cell": torch.full((1,), float(group["lr"]), device=dev),
              "lr_host": float(group["lr"]),
              "sizes": (ctypes.c_int * len(ps))(*sizes), "offs": (ctypes.c_int * len(ps))(*offs)}
+        steps = {}
+        for i, p in enumerate(ps):
+            st = self.state[p]
+            adopted = "exp_avg" in st and st["exp_avg"].numel() == p.numel() and "step" in st
+            # (a parameter without a state -- never updated under the optimizer that wrote it -- is at step 0)
+            steps.setdefault(float(st["step"]) if adopted else 0.0, i)
+        if len(steps) > 1 and any(self.state[p] for p in ps):
+            raise RuntimeError("FusedAdam: the adopted state has different step counts within one parameter group (%s); "
+                               "FusedAdam keeps one counter per group: put parameters with counts of their own into groups "
+                               "of their own" % ", ".join("parameter %d: step %g" % (i, s) for s, i in sorted(steps.items(),
+                                                                                                    key=lambda t: t[1])))
         step_view = f["step_cells"][0]
         for p, n, o in zip(ps, sizes, offs):
             st = self.state[p]

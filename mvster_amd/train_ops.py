@@ -327,15 +327,18 @@ class _ConvCL(torch.autograd.Function):
             else:
                 wargs = (xp, gyp, kernel, stride, padding)                                   # -> [cout, cin, k]
                 wkw = dict(co_keep=co, ci_keep=cin)
-            if leaf and _WGRAD_JOBS is not None:
+            if leaf and _WGRAD_JOBS is not None and _WGRAD_CTX.may_defer(weight):
                 # deferred_wgrad_finish: nothing reads this gradient before the backward pass is over, so the kernel itself
                 # waits for the end of the pass and runs there beside the other layers' (see the context manager)
                 dw = torch.empty(ops.conv_wgrad_shape(wargs[0], wargs[1], kernel, **wkw), device=gy.device, dtype=torch.float32)
                 _WGRAD_JOBS.append((wargs, wkw, dw, torch.cuda.current_stream(gy.device) if gy.is_cuda else None))
+                _WGRAD_CTX.queued[id(weight)] = _WGRAD_JOBS[-1]
                 if _WGRAD_EAGER is not None:
                     _WGRAD_EAGER.launch(wargs, wkw, dw)
                 gw = dw.view(dw.shape)           # (an alias: AccumulateGrad adopts a tensor only if nobody else holds it)
             else:
+                if leaf and _WGRAD_JOBS is not None:
+                    _WGRAD_CTX.settle(weight)    # (a second use of a weight: autograd adds the two gradients right away)
                 gw = ops.conv_wgrad(*wargs, **wkw)
             if weight.dim() == 4:
                 gw = gw.squeeze(2)
@@ -605,6 +608,22 @@ _WGRAD_STREAMS = {}
 _WGRAD_CTX = None            # the active deferred_wgrad_finish (for wgrad_flush_point)
 
 
+def side_stream(dev, avoid=()):
+    """A new HIP stream for the training step's concurrency that is none of the weight-gradient streams and none of
+    ``avoid``.  torch hands out its 32 pooled streams round-robin, so after enough ``torch.cuda.Stream()`` calls in one
+    process a "new" stream is one already in use: a stage's side stream could be a weight-gradient stream, or a captured
+    step's side stream its capture stream, whose joins then wait on themselves (in a long test process such a capture
+    ended in a host crash in hipGraph's capture end)."""
+    dev = torch.device(dev)
+    taken = list(_WGRAD_STREAMS.get(dev, [])) + list(avoid)
+    s = torch.cuda.Stream(device=dev)
+    for _ in range(64):                                  # (two turns of the pool at most)
+        if all(s != t for t in taken):
+            break
+        s = torch.cuda.Stream(device=dev)
+    return s
+
+
 class _FlushPoint(torch.autograd.Function):
     """Identity; its backward tells the active ``deferred_wgrad_finish(early=True)`` to launch what it has collected."""
 
@@ -638,7 +657,16 @@ class deferred_wgrad_finish:
     moved to a side stream) -- the kernels are persistent grids sized for an empty chip, and every cross-stream edge of the
     captured graph costs ~10 us.  The activations and output
     gradients the kernels read are kept alive until the join.  Plain ``loss.backward()`` outside the context runs every
-    layer on the spot."""
+    layer on the spot.
+
+    A postponed gradient is an unwritten buffer until the end of the pass, which is right only while autograd's
+    AccumulateGrad adopts it untouched.  A weight is therefore postponed only when its ``.grad`` is None (no accumulation
+    into an earlier gradient), it carries no tensor or post-accumulate hook (which would read the buffer), and no other
+    conv_cl use of it has been seen in this pass: at a weight's second use its postponed gradient is finished on the spot
+    (autograd adds the uses' gradients before the pass ends), and that use and every later one run inline.  Not detected: a
+    leaf weight that also feeds an operation other than conv_cl in the same graph (an L2 term on the weights added to the
+    loss, say) -- autograd adds that operation's gradient to the unwritten buffer; keep such terms out of the pass or
+    outside the context.  ``deferred`` counts the postponed gradients of the last pass."""
 
     def __init__(self, streams=1, overlap=False, policy="rr", early=False):
         self.nstreams = max(1, int(streams))
@@ -647,6 +675,50 @@ class deferred_wgrad_finish:
         self.policy = policy             # "rr": round-robin in autograd's order; "lpt": longest estimated job to the least loaded stream
         self._side = None
         self._pend = []
+        self.queued = {}                 # id(weight) -> its job, for the weights postponed in this pass and not yet settled
+        self.seen = set()                # id(weight) of every leaf weight a conv_cl backward met in this pass
+        self.deferred = 0
+
+    def may_defer(self, weight):
+        """True when ``weight``'s gradient can be postponed to the end of the pass (see the class docstring)."""
+        first = id(weight) not in self.seen
+        self.seen.add(id(weight))
+        return (first and weight.grad is None and not getattr(weight, "_backward_hooks", None)
+                and not getattr(weight, "_post_accumulate_grad_hooks", None))
+
+    def settle(self, weight):
+        """``weight`` is used again after its first gradient was postponed: finish that gradient now, in stream order before
+        whatever the current stream does next (autograd adds the uses' gradients as soon as the second arrives)."""
+        job = self.queued.pop(id(weight), None)
+        if job is None:
+            return
+        wargs, wkw, dw, src = job
+        cur = torch.cuda.current_stream(dw.device)
+        idx = next(i for i, j in enumerate(_WGRAD_JOBS) if j is job)
+        if not self.overlap and idx >= self._launched:
+            # not launched yet: run it whole on the stream its inputs were produced on, then join
+            del _WGRAD_JOBS[idx]
+            with torch.cuda.stream(src if src is not None else cur):
+                ops.conv_wgrad(*wargs, dw=dw, **wkw)
+            if src is not None and src != cur:
+                cur.wait_stream(src)
+            return
+        # launched on a side stream with its finish left to the batched launch: issue that finish alone there, then join
+        pairs = [(self._side, self._pend)] if self.overlap else list(zip(self._sides, self._pends))
+        for side, pend in pairs:
+            for r, rec in enumerate(pend):
+                if rec[1] is dw:
+                    del pend[r]
+                    prev = ops.WGRAD_PENDING
+                    ops.WGRAD_PENDING = [rec]
+                    try:
+                        with torch.cuda.stream(side):
+                            ops.conv_wgrad_flush()
+                    finally:
+                        ops.WGRAD_PENDING = prev
+                    cur.wait_stream(side)
+                    return
+        raise RuntimeError("deferred_wgrad_finish: lost the postponed gradient of a weight used twice")
 
     def __enter__(self):
         global _WGRAD_JOBS, _WGRAD_EAGER
@@ -657,6 +729,7 @@ class deferred_wgrad_finish:
         _WGRAD_EAGER = self if self.overlap else None
         _WGRAD_CTX = self
         self._side, self._pend = None, []
+        self.queued, self.seen, self.deferred = {}, set(), 0
         self._launched, self._sides, self._pends = 0, None, None
         return self
 
@@ -664,7 +737,7 @@ class deferred_wgrad_finish:
         if self._sides is None:
             pool = _WGRAD_STREAMS.setdefault(dev, [])
             while len(pool) < self.nstreams:
-                pool.append(torch.cuda.Stream(device=dev))
+                pool.append(side_stream(dev))
             self._sides = pool[:self.nstreams]
             self._pends = [[] for _ in self._sides]
         return self._sides
@@ -718,7 +791,7 @@ class deferred_wgrad_finish:
         if self._side is None:
             pool = _WGRAD_STREAMS.setdefault(dev, [])
             if not pool:
-                pool.append(torch.cuda.Stream(device=dev))
+                pool.append(side_stream(dev))
             self._side = pool[0]
         self._side.wait_stream(main)
         prev = ops.WGRAD_PENDING
@@ -734,6 +807,8 @@ class deferred_wgrad_finish:
         jobs = _WGRAD_JOBS
         eager, _WGRAD_EAGER = _WGRAD_EAGER, None
         _WGRAD_CTX = None
+        self.deferred = len(jobs) if jobs else 0
+        self.queued, self.seen = {}, set()
         try:
             return self._finish(exc_type, jobs, eager)
         finally:

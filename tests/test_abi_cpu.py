@@ -46,6 +46,44 @@ def test_null_and_shape_errors_are_reported_without_a_gpu(lib):
                                    None) == -1
 
 
+def test_fused_adam_checks_every_tensor_before_the_first_launch(lib):
+    """mvster_fused_adam over 200 tensors (two launches of <= 128) with a null grads[150] returns MVSTER_ERR_NULL; the
+    pointers are checked before anything is launched, so nothing of the first 128 tensors is updated (the GPU side of
+    this: tests/test_gpu_train.py::test_fused_adam_null_gradient_changes_nothing).  Negative sizes or offsets are
+    MVSTER_ERR_SHAPE.  Without a GPU the device pointers are stand-in addresses that nothing may dereference."""
+    import ctypes
+    from mvster_amd import _lib
+    n = 200
+    if torch.cuda.is_available():
+        keep = torch.zeros(3 * n * 64 + 3, device="cuda")
+        base, stride = keep.data_ptr(), 64 * 4
+    else:
+        base, stride = 1 << 32, 64 * 4
+    dev = [base + stride * i for i in range(3 * n)]
+    pp = (ctypes.c_void_p * n)(*dev[:n])
+    gp = (ctypes.c_void_p * n)(*dev[n:2 * n])
+    sizes = (ctypes.c_int * n)(*[64] * n)
+    offs = (ctypes.c_int * n)(*[64 * i for i in range(n)])
+    cells = base + stride * 3 * n
+
+    def call(count=n):
+        return lib.mvster_fused_adam(ctypes.cast(pp, ctypes.c_void_p), ctypes.cast(gp, ctypes.c_void_p),
+                                     ctypes.cast(sizes, ctypes.c_void_p), ctypes.cast(offs, ctypes.c_void_p), count,
+                                     dev[2 * n], dev[2 * n], cells, cells + 8, 0.9, 0.999, 1e-8, 0.0, None)
+    gp[150] = None
+    assert call() == _lib.ERR_NULL
+    gp[150] = dev[n + 150]
+    pp[199] = None
+    assert call() == _lib.ERR_NULL
+    pp[199] = dev[199]
+    sizes[170] = -1
+    assert call() == _lib.ERR_SHAPE
+    sizes[170] = 64
+    offs[130] = -64
+    assert call() == _lib.ERR_SHAPE
+    assert call(0) == _lib.ERR_SHAPE
+
+
 def test_product_has_no_cpu_fallback(shipped_cfg):
     from mvster_amd import MVS4net, ops
     from mvster_amd.synthetic import make_inputs

@@ -364,6 +364,87 @@ def test_fused_sinkhorn_vs_tensor_form(D, iters, eps, cont):
     assert (ag.grad.cpu()[~mask.unsqueeze(1).expand_as(attn)] == 0).all()
 
 
+def _sinkhorn_vs_fp64(D, iters, eps, cont):
+    """The data of test_fused_sinkhorn_vs_tensor_form; -> (kernel, loss, loss rel. error, gradient rel. L2, gradient,
+    mask of the masked-out entries)."""
+    from mvster_amd import _lib
+    from mvster_amd.loss import sinkhorn_loss
+    g = torch.Generator().manual_seed(D * 10 + iters)
+    B, H, W = 2, 13, 17
+    attn = torch.softmax(3 * torch.randn(B, D, H, W, generator=g), 1)
+    inv = 1.0 / 900 + 2e-5 * (torch.arange(D).view(1, D, 1, 1) + 0.1 * torch.rand(B, D, H, W, generator=g))
+    hypo = (1.0 / inv).float()
+    gt = (1.0 / (1.0 / 900 + 2e-5 * (-1.0 + (D + 1) * torch.rand(B, H, W, generator=g)))).float()
+    mask = torch.rand(B, H, W, generator=g) > 0.3
+    gt[~mask] = 0.0
+    ad = attn.double().requires_grad_(True)
+    want = O.sinkhorn(gt.double(), hypo.double(), ad, mask, iters, eps, continuous=cont)[1]
+    want.backward()
+    ag = attn.to(DEV).requires_grad_(True)
+    got = sinkhorn_loss(gt.to(DEV), hypo.to(DEV), ag, mask.to(DEV), iters, eps, continuous=cont)
+    kernel = _lib.last_kernel()
+    got.backward()
+    torch.cuda.synchronize()
+    e_l = abs(got.item() - want.item()) / abs(want.item())
+    e_g = ((ag.grad.cpu().double() - ad.grad).norm() / ad.grad.norm()).item()
+    return kernel, got.item(), e_l, e_g, ag.grad.cpu(), mask.unsqueeze(1).expand_as(attn)
+
+
+def _sinkhorn_tolerances(D, eps, cont):
+    """(loss, gradient) bounds against fp64, fitted on the measured grid (D 3 / 4 / 5 / 8 / 12, discrete and continuous,
+    3 / 10 / 16 iterations).  The potentials reach about c/eps + 28 (the largest cost over eps plus |log 1e-12|), and each
+    fp32 update rounds them relative to that size.  The loss, a plan-weighted sum, stays within the 2e-5 of the eps >= 0.5
+    cases everywhere (measured <= 2.1e-6).  The gradient runs the rounding back through the reverse sweep, whose softmax
+    Jacobians sharpen as eps falls; worst measured relative L2 error per eps over the grid: 5.2e-5 for eps >= 0.07, 2.2e-4 at
+    0.05, 8.4e-4 at 0.03 (D = 3 continuous, 16 iterations).  The bounds: 2e-4 (that of the eps >= 0.5 cases) down to
+    eps = 0.07, then four times the worst measured value (about 5e-4 / 1e-3 / 3.4e-3 above 0.05 / 0.03)."""
+    if eps >= 0.07:
+        tol_g = 2e-4
+    elif eps >= 0.05:
+        tol_g = 1e-3
+    elif eps >= 0.03:
+        tol_g = 3.4e-3
+    else:
+        raise ValueError("no measured bound below eps = 0.03")
+    return 2e-5, tol_g
+
+
+SMALL_EPS = (0.25, 0.1, 0.07, 0.05, 0.03)
+SMALL_EPS_CASES = [(D, cont) for D in (4, 8) for cont in (False,)] + [(D, cont) for D in (3, 5, 12) for cont in (False, True)]
+
+
+@pytest.mark.parametrize("iters", [3, 10, 16])
+@pytest.mark.parametrize("eps", SMALL_EPS)
+@pytest.mark.parametrize("D,cont", SMALL_EPS_CASES, ids=["D%d%s" % (D, "_cont" if c else "") for D, c in SMALL_EPS_CASES])
+def test_fused_sinkhorn_small_eps_vs_fp64(D, cont, eps, iters):
+    """The fused Sinkhorn kernels at a small entropic regularisation (``--ot_eps``) against the fp64 tensor form: the
+    factored kernel (D = 4 / 8, discrete) keeps exp(k / eps) unshifted, which overflows fp32 at (D-1)/eps > 88 and gave a
+    NaN loss there; the dispatch now sends such eps to the max-shifted general kernel.  Finite loss and gradient, exactly
+    zero gradient on masked pixels, and the errors within ``_sinkhorn_tolerances``."""
+    kernel, loss, e_l, e_g, grad, masked = _sinkhorn_vs_fp64(D, iters, eps, cont)
+    tol_l, tol_g = _sinkhorn_tolerances(D, eps, cont)
+    note("sinkhorn_small_eps_D%d%s_eps%g_it%d" % (D, "_cont" if cont else "", eps, iters), kernel=kernel, loss_rel=e_l,
+         grad_rel_l2=e_g, tol_loss=tol_l, tol_grad=tol_g)
+    assert torch.isfinite(torch.tensor(loss)) and torch.isfinite(grad).all(), (kernel, loss)
+    assert (grad[~masked] == 0).all()
+    assert e_l <= tol_l and e_g <= tol_g, (kernel, e_l, e_g)
+
+
+@pytest.mark.parametrize("D", [4, 8])
+def test_fused_sinkhorn_fast_kernel_cutoff(D):
+    """The dispatch boundary: the factored kernel while (D-1)/eps < 60, the general one from there on -- eps 2 % on either
+    side of (D-1)/60, and the shipped eps = 1 on the factored kernel; both sides within the bounds of the small-eps test."""
+    cut = (D - 1) / 60.0
+    for eps, want in ((1.0, "sinkhorn_fast_kernel<%d>" % D), (cut * 1.02, "sinkhorn_fast_kernel<%d>" % D),
+                      (cut * 0.98, "sinkhorn_kernel<%d, false>" % D)):
+        kernel, loss, e_l, e_g, grad, masked = _sinkhorn_vs_fp64(D, 10, eps, False)
+        tol_l, tol_g = _sinkhorn_tolerances(D, eps, False)
+        note("sinkhorn_cutoff_D%d_eps%.5f" % (D, eps), kernel=kernel, loss_rel=e_l, grad_rel_l2=e_g, tol_loss=tol_l, tol_grad=tol_g)
+        assert kernel == want, (eps, kernel)
+        assert torch.isfinite(grad).all() and (grad[~masked] == 0).all()
+        assert e_l <= tol_l and e_g <= tol_g, (eps, kernel, e_l, e_g)
+
+
 def test_fused_sinkhorn_vs_reference_values(golden):
     """The fused kernels against what the reference's own ``sinkhorn`` returned (fixtures G8 discrete, G8b continuous)."""
     from mvster_amd.loss import sinkhorn_loss
@@ -729,11 +810,11 @@ def test_graphed_train_step_follows_the_eager_trajectory():
     assert other != before
 
 
-def _small_train_setup(seed_sd=6, H=128, W=192, N=3, B=2):
+def _small_train_setup(seed_sd=6, H=128, W=192, N=3, B=2, mono=True):
     from mvster_amd.synthetic import randomize_state
     cfg = dict(arch_mode="fpn", reg_net="reg2d", num_stage=4, fpn_base_channel=8, reg_channel=8, stage_splits=[8, 8, 4, 4],
                depth_interals_ratio=[0.5, 0.5, 0.5, 1], group_cor=True, group_cor_dim=[8, 8, 4, 4], inverse_depth=True,
-               mono=True, attn_temp=2, attn_fuse_d=True)
+               mono=mono, attn_temp=2, attn_fuse_d=True)
     torch.manual_seed(4)
     sd = randomize_state(MVS4net(**cfg).state_dict(), seed=seed_sd, prob_gain=4.0)
     imgs, proj, dv = make_inputs(nviews=N, H=H, W=W, seed=3, batch=B)
@@ -746,7 +827,7 @@ def _small_train_setup(seed_sd=6, H=128, W=192, N=3, B=2):
 
     def loss_fn(o, g_, m_):
         return MVS4net_loss(o, g_, m_, stage_lw=[1, 1, 1, 1], l1ot_lw=[0, 1], inverse_depth=True, ot_iter=10, ot_eps=1,
-                            ot_continous=False, mono=True)
+                            ot_continous=False, mono=mono)
 
     def build():
         m = MVS4net(**cfg)
@@ -809,6 +890,108 @@ def test_side_stream_stages_give_the_main_stream_step():
         assert want[2].keys() == got[2].keys()
         for k in want[2]:
             assert torch.equal(want[2][k], got[2][k]), k
+
+
+@pytest.mark.parametrize("widen", [False, True], ids=["plain", "side_stream_delayed"])
+def test_side_stream_stages_give_the_main_stream_step_without_mono(monkeypatch, widen):
+    """test_side_stream_stages_give_the_main_stream_step with mono=False (the model's default): then nothing but autograd
+    holds the pyramid levels that the side-stream stages' warp backward reads (allocated on the main or the FPN's tail
+    stream), and without record_stream their blocks go back to those streams' pools as soon as that backward is enqueued.
+    Same five stream configurations, loss, stage depths and every gradient bit-equal to the one-stream step.
+    ``side_stream_delayed``: a ~1 ms spin on the stream at the start of every warp backward widens the window in which a
+    reused block would be overwritten before it is read."""
+    from mvster_amd.net import _WarpAggPyr
+    if widen:
+        plain = _WarpAggPyr.backward
+
+        def delayed(ctx, *grads):
+            torch.cuda._sleep(2_000_000)                    # (cycles of the spin kernel: about a millisecond)
+            return plain(ctx, *grads)
+        monkeypatch.setattr(_WarpAggPyr, "backward", staticmethod(delayed))
+    build, loss_fn, (imgs, proj, dv, gt, mask) = _small_train_setup(mono=False)
+    runs = []
+    for stages, separate, tail in (((), False, False), ((0, 1, 2), False, True), ((0, 1, 2), True, False), ((1, 3), False, True),
+                                   ((), False, True)):
+        m = build()
+        m.train_side_stages, m.train_side_separate, m.train_fpn_tail_stream = stages, separate, tail
+        out = m(imgs, proj, dv)
+        loss = loss_fn(out, gt, mask)[0]
+        depths = [out["stage%d" % (s + 1)]["depth"] for s in range(4)]
+        del out
+        loss.backward()
+        torch.cuda.synchronize()
+        runs.append((loss.detach().clone(), [d.detach().clone() for d in depths],
+                     {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}))
+    want = runs[0]
+    for i, got in enumerate(runs[1:]):
+        assert torch.equal(want[0], got[0]), i
+        assert all(torch.equal(a, b) for a, b in zip(want[1], got[1])), i
+        assert want[2].keys() == got[2].keys()
+        for k in want[2]:
+            assert torch.equal(want[2][k], got[2][k]), (i, k)
+
+
+def test_graphed_step_gradients_equal_eager_gradients_without_mono(monkeypatch):
+    """test_graphed_step_gradients_equal_eager_gradients with mono=False (side-stream stages, nothing else holding the
+    pyramid): a block freed inside the capture goes to the capture's later allocations, so without record_stream on the
+    levels the captured step's gradients were far off (largest difference 2.9 times the largest gradient).  Against the
+    eager one-stream step, deterministic warp backward, zero learning rate."""
+    from mvster_amd.graph import GraphedTrainStep
+    monkeypatch.setenv("MVSTER_BWD_DETERMINISTIC", "1")
+    build, loss_fn, (imgs, proj, dv, gt, mask) = _small_train_setup(mono=False)
+    m1 = build()
+    m1.train_side_stages, m1.train_fpn_tail_stream = (), False
+    loss_fn(m1(imgs, proj, dv), gt, mask)[0].backward()
+    m2 = build()
+    opt = torch.optim.Adam(m2.parameters(), lr=0.0, capturable=True)
+    step = GraphedTrainStep(m2, opt, loss_fn, imgs, proj, dv, gt, mask, warmup=2)
+    step()
+    torch.cuda.synchronize()
+    g1 = {k: p.grad for k, p in m1.named_parameters()}
+    g2 = {k: p.grad for k, p in m2.named_parameters()}
+    assert all((g1[k] is None) == (g2[k] is None) for k in g1)
+    scale = max(v.abs().max().item() for v in g1.values() if v is not None)
+    worst, worst_name = 0.0, ""
+    for k, v in g1.items():
+        if v is None:
+            continue
+        e = (g2[k] - v).abs().max().item() / scale
+        if e > worst:
+            worst, worst_name = e, k
+    note("graphed_vs_eager_gradients_no_mono", worst_abs_over_global_max=worst, worst=worst_name, tensors=len(g1))
+    assert worst <= 1e-5, (worst_name, worst)
+
+
+def test_training_side_streams_are_distinct():
+    """torch hands out its pooled streams round-robin: after 32 ``torch.cuda.Stream()`` a new one is an old one.  The
+    training step's side streams (train_ops.side_stream) are none of the weight-gradient streams, the current stream or
+    the model's other streams, however many streams the process made before."""
+    ctx = T.deferred_wgrad_finish(streams=2)
+    with ctx:
+        ctx._streams(DEV)                                                 # (creates the weight-gradient streams)
+    wgrad = list(T._WGRAD_STREAMS[DEV])
+    for _ in range(40):                                                   # (turn the pool to every offset)
+        torch.cuda.Stream()
+        s = T.side_stream(DEV, avoid=[torch.cuda.current_stream()])
+        assert all(s != w for w in wgrad) and s != torch.cuda.current_stream()
+        others = [T.side_stream(DEV, avoid=[s])]
+        assert others[0] != s and all(others[0] != w for w in wgrad)
+
+
+def test_graphed_step_refuses_to_replay_after_optimizer_load_state_dict():
+    """The captured step updates the optimizer's state tensors by address; load_state_dict replaces them (FusedAdam: its flat
+    buffers and the step cell), so the graph would keep updating the old ones.  The replay raises instead."""
+    from mvster_amd.graph import GraphedTrainStep
+    from mvster_amd.optim import FusedAdam
+    build, loss_fn, (imgs, proj, dv, gt, mask) = _small_train_setup(seed_sd=9)
+    m = build()
+    opt = FusedAdam(m.parameters(), lr=1e-4)
+    step = GraphedTrainStep(m, opt, loss_fn, imgs, proj, dv, gt, mask, warmup=1)
+    step()
+    torch.cuda.synchronize()
+    opt.load_state_dict(opt.state_dict())
+    with pytest.raises(RuntimeError, match="load_state_dict"):
+        step()
 
 
 def test_eager_forward_after_graph_replays_sees_the_updated_weights():
@@ -992,6 +1175,135 @@ def test_deferred_weight_gradients_equal_the_inline_ones():
     assert T._WGRAD_JOBS is None and T._WGRAD_EAGER is None and T._WGRAD_CTX is None and ops.WGRAD_PENDING is None
 
 
+SHIPPED_DEFERRED_WGRADS = 62     # weight gradients GraphedTrainStep's context postponed in _small_train_setup's step before
+                                 # the preconditions (counted on the parent commit; 2 more, of derived weights, run inline)
+
+
+def _deferred_forms():
+    """Every form of deferred_wgrad_finish test_deferred_weight_gradients_equal_the_inline_ones runs."""
+    return (T.deferred_wgrad_finish(streams=1), T.deferred_wgrad_finish(streams=2), T.deferred_wgrad_finish(streams=3),
+            T.deferred_wgrad_finish(overlap=True), T.deferred_wgrad_finish(streams=2, early=True),
+            T.deferred_wgrad_finish(streams=1, early=True), T.deferred_wgrad_finish(streams=3, early=True, policy="lpt"))
+
+
+def _deferred_precondition_case(kind):
+    """Three-layer channels-last chain x -> w0 -> flush point -> w1 -> w2 -> <y, gy>, with w1 = w0 for kind "shared"
+    (one leaf weight in two conv_cl calls), two passes without zero_grad for "accumulate", and a tensor hook plus a
+    post-accumulate-grad hook on w1 for "hooks"; x -> w0 -> flush point -> w0 -> w0 -> w2 for "triple" (one weight in
+    three calls).  -> (run(ctx) -> gradients [+ what the hooks saw], the fp64 CPU gradients of the same sums)."""
+    g = torch.Generator().manual_seed(11)
+    w0 = 0.2 * torch.randn(16, 16, 1, 3, 3, generator=g)
+    w1 = 0.2 * torch.randn(16, 16, 1, 3, 3, generator=g)
+    w2 = 0.2 * torch.randn(8, 16, 1, 3, 3, generator=g)          # (8 outputs: the mirrored weight-gradient form)
+    xs = [torch.randn(2, 2, 24, 40, 16, generator=g) for _ in range(2 if kind == "accumulate" else 1)]
+    gy = torch.randn(2, 2, 24, 40, 8, generator=g)
+    pad = (0, 1, 1)
+
+    def layers(ws):
+        if kind == "shared":
+            return [ws[0], ws[0], ws[1]]
+        if kind == "triple":
+            return [ws[0], ws[0], ws[0], ws[1]]
+        return list(ws)
+
+    def run(ctx):
+        params = [w.to(DEV).requires_grad_(True) for w in ((w0, w2) if kind in ("shared", "triple") else (w0, w1, w2))]
+        chain = layers(params)
+        seen = []
+        if kind == "hooks":
+            chain[1].register_hook(lambda gr: seen.append(gr.clone()))
+            chain[1].register_post_accumulate_grad_hook(lambda p: seen.append(p.grad.clone()))
+        xg = [x.to(DEV).requires_grad_(True) for x in xs]
+        for x in xg:
+            y = T.conv_cl(x, chain[0], None, 1, pad)
+            y = T.wgrad_flush_point(y)
+            for w in chain[1:]:
+                y = T.conv_cl(y, w, None, 1, pad)
+            loss = (y * gy.to(DEV)).sum()
+            if ctx is None:
+                loss.backward()
+            else:
+                with ctx:
+                    loss.backward()
+        torch.cuda.synchronize()
+        return [x.grad.clone() for x in xg] + [p.grad.clone() for p in params] + seen
+
+    def cf(t):
+        return t.permute(0, 4, 1, 2, 3)
+    wd = [w.double().requires_grad_(True) for w in ((w0, w2) if kind in ("shared", "triple") else (w0, w1, w2))]
+    chain = layers(wd)
+    xd = [cf(x).double().requires_grad_(True) for x in xs]
+    for x in xd:
+        y = x
+        for w in chain:
+            y = F.conv3d(y, w, padding=pad)
+        (y * cf(gy).double()).sum().backward()
+    ref = [x.grad.permute(0, 2, 3, 4, 1) for x in xd] + [w.grad for w in wd]
+    return run, ref
+
+
+@pytest.mark.parametrize("kind", ["shared", "triple", "accumulate", "hooks"])
+def test_deferred_weight_gradients_preconditions(kind):
+    """deferred_wgrad_finish hands AccumulateGrad an unwritten buffer that the postponed kernel fills at the end of the pass;
+    that is right only if autograd adopts it untouched.  A weight used by two conv_cl calls (autograd adds the two
+    gradients at once), a ``.grad`` kept from an earlier pass (``grad += new``) and a hook on the weight (it reads the
+    gradient) all read the buffer before it is written.  Under every context form: each gradient equals the plain
+    backward's bit for bit, what the hooks saw equals the final gradient, and all of it meets fp64 conv3d autograd within
+    the bounds of test_conv_cl_forward_and_gradients."""
+    run, ref = _deferred_precondition_case(kind)
+    want = run(None)
+    nx = len(ref) - (2 if kind in ("shared", "triple") else 3)
+
+    def rel(a, r):
+        return ((a.cpu().double() - r).abs().max() / (r.abs().max() + 1e-30)).item()
+    errs = [rel(a, r) for a, r in zip(want, ref)]
+    note("deferred_precondition_" + kind, rel_max=errs)
+    assert all(e <= 1e-5 for e in errs[:nx]) and all(e <= 2e-5 for e in errs[nx:]), errs
+    if kind == "hooks":
+        final = want[nx + 1]                                                         # w1's gradient
+        assert torch.equal(want[-2], final) and torch.equal(want[-1], final)         # what the hooks saw
+    for ctx in _deferred_forms():
+        got = run(ctx)
+        assert len(got) == len(want)
+        for i, (a, b) in enumerate(zip(want, got)):
+            assert torch.equal(a, b), (kind, ctx.nstreams, ctx.overlap, ctx.early, i)
+    assert T._WGRAD_JOBS is None and T._WGRAD_EAGER is None and T._WGRAD_CTX is None and ops.WGRAD_PENDING is None
+
+
+def test_deferred_weight_gradients_of_the_training_step(monkeypatch):
+    """The preconditions above cost the shipped step nothing: inside GraphedTrainStep's context form the training step of
+    _small_train_setup postpones exactly the weight gradients the unconditional form postponed (no weight of it is used
+    twice or hooked, no gradient pre-exists), runs the same number inline, and every gradient is the same bits."""
+    build, loss_fn, (imgs, proj, dv, gt, mask) = _small_train_setup()
+    counts = {}
+    real = ops.conv_wgrad
+
+    def counting(*a, **kw):
+        key = "deferred" if kw.get("may_defer") else "inline"
+        counts[key] = counts.get(key, 0) + 1
+        return real(*a, **kw)
+    monkeypatch.setattr(ops, "conv_wgrad", counting)
+
+    def run():
+        counts.clear()
+        m = build()
+        loss = loss_fn(m(imgs, proj, dv), gt, mask)[0]
+        ctx = T.deferred_wgrad_finish(streams=2, early=True)
+        with ctx:
+            loss.backward()
+        torch.cuda.synchronize()
+        assert ctx.deferred == counts.get("deferred", 0)
+        return dict(counts), {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}
+    got_counts, got = run()
+    note("deferred_training_step", **got_counts)
+    monkeypatch.setattr(T.deferred_wgrad_finish, "may_defer", lambda self, w: True)         # the unconditional form
+    want_counts, want = run()
+    assert got_counts == want_counts and got_counts.get("deferred", 0) == SHIPPED_DEFERRED_WGRADS, got_counts
+    assert want.keys() == got.keys()
+    for k in want:
+        assert torch.equal(want[k], got[k]), k
+
+
 @pytest.mark.parametrize("lw,l1ot", [([1, 1, 1, 1], [0, 1]), ([0.5, 1.0, 1.5, 2.0], [0.3, 0.7])])
 def test_loss_total_chain_vs_tensor_form(lw, l1ot):
     """MVS4net_loss's weighted total carried through the stages' fused kernels (mvster_stage_loss_fwd / _bwd) against the
@@ -1143,6 +1455,81 @@ def test_fused_adam_follows_torch_adam(wd):
     worst = max(((a - b).abs().max() / b.abs().max().clamp_min(1e-6)).item() for a, b in zip(pc, pb))
     assert worst <= 2e-6, worst
     assert float(oc.state_dict()["state"][0]["step"]) == 6.0
+
+
+def test_fused_adam_refuses_a_state_with_different_steps():
+    """FusedAdam keeps one step counter per group.  A torch.optim.Adam state in which the parameters of one group have
+    different ``step`` counts (a parameter frozen for part of training) used to be collapsed onto the last parameter's
+    count; the first step() after load_state_dict now raises and names the mismatch, and leaves the parameters alone."""
+    from mvster_amd.optim import FusedAdam
+    g = torch.Generator().manual_seed(2)
+    shapes = [(8, 3, 3), (16,), (5, 7), (33,)]
+    pb = [torch.nn.Parameter(torch.randn(s, generator=g).to(DEV)) for s in shapes]
+    ob = torch.optim.Adam(pb, lr=1e-2)
+    for it in range(3):
+        for i, p in enumerate(pb):
+            p.grad = torch.randn(p.shape, generator=g).to(DEV) if (it < 2 or i != 2) else None
+        ob.step()
+    sd = ob.state_dict()
+    assert sorted(float(sd["state"][i]["step"]) for i in range(4)) == [2.0, 3.0, 3.0, 3.0]
+    pc = [torch.nn.Parameter(p.detach().clone()) for p in pb]
+    oc = FusedAdam(pc, lr=1e-2)
+    oc.load_state_dict(sd)
+    for p in pc:
+        p.grad = torch.ones_like(p)
+    before = [p.detach().clone() for p in pc]
+    with pytest.raises(RuntimeError, match=r"different step counts.*parameter 0: step 3.*parameter 2: step 2"):
+        oc.step()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, p.detach()) for a, p in zip(before, pc))
+    # a parameter that never had a gradient under torch's Adam has no state: step 0, a mismatch as well
+    pd = [torch.nn.Parameter(torch.randn(s, generator=g).to(DEV)) for s in shapes]
+    od = torch.optim.Adam(pd, lr=1e-2)
+    for _ in range(2):
+        for i, p in enumerate(pd):
+            p.grad = torch.randn(p.shape, generator=g).to(DEV) if i != 3 else None
+        od.step()
+    assert 3 not in od.state_dict()["state"]
+    pe = [torch.nn.Parameter(p.detach().clone()) for p in pd]
+    oe = FusedAdam(pe, lr=1e-2)
+    oe.load_state_dict(od.state_dict())
+    for p in pe:
+        p.grad = torch.ones_like(p)
+    with pytest.raises(RuntimeError, match=r"parameter 0: step 2.*parameter 3: step 0"):
+        oe.step()
+
+
+def _fused_adam_null_call(n, null_at, params, grads, exp_avg, exp_avg_sq, step_cells, lr_cell):
+    import ctypes
+    from mvster_amd import _lib
+    pp = (ctypes.c_void_p * n)(*[p.data_ptr() for p in params])
+    gp = (ctypes.c_void_p * n)(*[gr.data_ptr() for gr in grads])
+    gp[null_at] = None
+    sizes = (ctypes.c_int * n)(*[p.numel() for p in params])
+    offs = (ctypes.c_int * n)(*[i * 64 for i in range(n)])
+    return _lib.load().mvster_fused_adam(ctypes.cast(pp, ctypes.c_void_p), ctypes.cast(gp, ctypes.c_void_p),
+                                         ctypes.cast(sizes, ctypes.c_void_p), ctypes.cast(offs, ctypes.c_void_p), n,
+                                         exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step_cells.data_ptr(), lr_cell.data_ptr(),
+                                         0.9, 0.999, 1e-8, 0.0, None)
+
+
+def test_fused_adam_null_gradient_changes_nothing():
+    """mvster_fused_adam over 200 tensors (two launches of <= 128) with a null grads[150]: MVSTER_ERR_NULL, and -- because
+    every pointer is checked before the first launch -- the first 128 parameters, the moments and the step cell are the
+    same bits after a synchronize (the null used to be found after the first launch had updated them)."""
+    g = torch.Generator().manual_seed(3)
+    n = 200
+    params = [torch.randn(64, generator=g).to(DEV) for _ in range(n)]
+    grads = [torch.randn(64, generator=g).to(DEV) for _ in range(n)]
+    exp_avg = torch.rand(n * 64, generator=g).to(DEV)
+    exp_avg_sq = torch.rand(n * 64, generator=g).to(DEV)
+    step_cells = torch.tensor([4.0, 0.0], device=DEV)
+    lr_cell = torch.tensor([1e-2], device=DEV)
+    before = [t.clone() for t in params + [exp_avg, exp_avg_sq, step_cells]]
+    assert _fused_adam_null_call(n, 150, params, grads, exp_avg, exp_avg_sq, step_cells, lr_cell) == -1     # MVSTER_ERR_NULL
+    torch.cuda.synchronize()
+    after = params + [exp_avg, exp_avg_sq, step_cells]
+    assert all(torch.equal(a, b) for a, b in zip(before, after))
 
 
 @pytest.mark.parametrize("shape,groups,relu,with_skip", [((2, 8, 8, 10, 64), 1, True, True), ((2, 4, 64, 80, 16), 1, True, False),

@@ -78,3 +78,20 @@ def test_loss_on_golden_train_outputs(golden, tensor_level_ot):
     assert abs(loss.item() - float(g.np("loss"))) <= 1e-5 * abs(float(g.np("loss")))
     assert torch.allclose(torch.stack(ots), g.t("ot"), rtol=1e-5)
     assert torch.allclose(torch.stack(l1s), g.t("l1"), rtol=1e-5)
+
+
+@pytest.mark.parametrize("eps", [0, 0.0, -1.0, float("nan"), 1e-39])
+def test_losses_reject_a_nonpositive_eps(eps):
+    """eps <= 0 (or NaN, or so small that 1 / eps overflows fp32) has no transport plan: the kernels would scale the cost by
+    an infinite 1 / eps.  sinkhorn_loss and the per-stage losses raise ValueError before any device work (CPU tensors here)."""
+    B, D, H, W = 1, 4, 2, 3
+    attn = torch.full((B, D, H, W), 0.25)
+    hypo = torch.arange(1.0, D + 1).view(1, D, 1, 1).expand(B, D, H, W).contiguous()
+    gt = torch.full((B, H, W), 2.0)
+    mask = torch.ones(B, H, W)
+    with pytest.raises(ValueError, match="eps"):
+        L.sinkhorn_loss(gt, hypo, attn, mask, 3, eps)
+    with pytest.raises(ValueError, match="eps"):
+        L.stage_losses(gt, hypo, attn, mask, iters=3, eps=eps)
+    with pytest.raises(ValueError, match="eps"):
+        MVS4net_loss({"stage1": {"hypo_depth": hypo, "attn_weight": attn}}, {"stage1": gt}, {"stage1": mask}, ot_eps=eps)
