@@ -404,6 +404,38 @@ int mvster_geo_filter(const float* depth_ref, const float* depth_src, const doub
                       int* mask_sum, float* depth_sum, unsigned char* view_mask, float* view_depth, float* x_src,
                       float* y_src, int NS, int H, int W, float pix_thres, float rel_thres, void* stream);
 
+/* ---- depth-map fusion of a whole scan (csrc/geo_scene.hip): filter_depth of test_mvs4.py:331-421 in three launches ---- */
+
+/* Number of workgroups (= survivor counts) the scene kernels use for R reference views of H x W pixels: the length of
+ * wg_counts; wg_offsets holds one more.  MVSTER_ERR_SHAPE for non-positive sizes or more than 2^31 - 2 workgroups. */
+int mvster_geo_scene_blocks(int R, int H, int W);
+
+/* Filter pass + scan.  depth / confidence [V,H,W]: every view of the scan once; pairs [R,Smax] int32 = source views of
+ * each reference view in pair-file order, padded with -1; ref_view [R] int32; ref_mats [R][30] = inv(K_ref)[9], K_ref[9],
+ * inv(E_ref)[3x4]; view_mats [R][Smax][42] laid out as for mvster_geo_filter (rows behind the padding are not read).
+ * One thread per (reference view, pixel) walks its source list like mvster_geo_filter (test_mvs4.py:362-385) and writes
+ * mask_sum [R,H,W] int32, depth_avg [R,H,W] double = (float32 depth sum + depth_ref) / (votes + 1) (:385), and the 0 / 1
+ * byte masks photo = confidence > conf_thres (:361), geo = votes >= thres_view (:387), final = both (:388).  wg_counts
+ * [mvster_geo_scene_blocks()] int32 (scratch) = survivors per workgroup; wg_offsets [blocks + 1] int64 = their exclusive
+ * scan, wg_offsets[blocks] = number of points M.  A workgroup covers 256 consecutive pixels of one view, so view r's
+ * survivors are wg_offsets[(r + 1) * blocks / R] - wg_offsets[r * blocks / R].  View indices outside [0, V) are never
+ * dereferenced (such a reference view keeps nothing; such a source entry ends the list).  Two launches, no atomics. */
+int mvster_geo_scene_filter(const float* depth, const float* confidence, const int* pairs, const int* ref_view,
+                            const double* ref_mats, const double* view_mats, int* mask_sum, double* depth_avg,
+                            unsigned char* photo_mask, unsigned char* geo_mask, unsigned char* final_mask, int* wg_counts,
+                            long* wg_offsets, int R, int Smax, int V, int H, int W, float conf_thres, int thres_view,
+                            float pix_thres, float rel_thres, void* stream);
+
+/* Emit pass: the pixels of final_mask, reference views in order and row-major inside a view, lifted to world space
+ * with depth_avg in fp64 and rounded once -> points [M,3] float32 (test_mvs4.py:397-407, :413-415); colors [M,3] uint8 =
+ * (image * 255) truncated (:395-396, :407).  images [V,H,W,3]: image_kind 0 = uint8 (copied: the float32 round trip
+ * v / 255 * 255 is the identity on all 256 values), 1 = float32 in 0..1; anything else is MVSTER_ERR_UNSUPPORTED.
+ * depth_avg / final_mask / ref_view / ref_mats / wg_offsets as written by (given to) mvster_geo_scene_filter with the
+ * same R, H, W; M = wg_offsets[blocks] read back by the caller (points beyond M are dropped, M = 0 launches nothing). */
+int mvster_geo_scene_emit(const double* depth_avg, const unsigned char* final_mask, const int* ref_view,
+                          const double* ref_mats, const void* images, int image_kind, const long* wg_offsets, float* points,
+                          unsigned char* colors, long M, int R, int V, int H, int W, void* stream);
+
 /* ---- training-step glue (csrc/train_glue.hip): the reference's chains of small tensor expressions, one launch each ---- */
 
 /* One stage of MVS4net_loss around the OT term (models/MVS4Net.py:126-153), forward: hypo [B,D,HW] (D >= 3), gt, mask

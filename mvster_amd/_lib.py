@@ -83,6 +83,9 @@ SIGNATURES = {
     "mvster_fine_weights_bwd": [_f] * 9 + [_i, _i, _i, _f],
     "mvster_fused_adam": [_f, _f, _f, _f, _i, _f, _f, _f, _f] + [ctypes.c_double] * 4 + [_f],
     "mvster_geo_filter": [_f] * 10 + [_i, _i, _i, _fl, _fl, _f],
+    "mvster_geo_scene_blocks": [_i, _i, _i],
+    "mvster_geo_scene_filter": [_f] * 13 + [_i] * 5 + [_fl, _i, _fl, _fl, _f],
+    "mvster_geo_scene_emit": [_f] * 5 + [_i, _f, _f, _f, _l, _i, _i, _i, _i, _f],
     "mvster_mfma_probe": [_f, _f, _f, _f],
     "mvster_gather_batch": [_f, _i, _i, _f],
     "mvster_last_kernel": [],

@@ -5,11 +5,18 @@ Mirrors the reference's ``test_mvs4.py`` functions -- ``check_geometric_consiste
 gfx950 kernel (``mvster_geo_filter``) instead of NumPy + ``cv2.remap`` per view pair.  Inputs may be NumPy arrays
 (as in the reference) or torch tensors; NumPy in gives NumPy out.  The small camera-matrix algebra stays on the host
 in NumPy float32, exactly as the reference computes it; everything per pixel runs on the GPU.
+
+A whole scan -- the reference's unit of work (``filter_depth``, test_mvs4.py:331-421) -- goes through ``fuse_scene`` /
+``filter_depth``: every map is uploaded once and three launches (``mvster_geo_scene_filter`` = filter pass + scan of the
+workgroup counts, ``mvster_geo_scene_emit``) produce the masks and the point cloud in the reference's order.
 """
+import collections
+import os
+
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, formats
 
 
 def _np32(a):
@@ -150,3 +157,195 @@ def read_ply(filename):
     if "format binary_little_endian 1.0" not in head:
         raise RuntimeError("read_ply: only the binary little-endian layout of write_ply is read")
     return np.frombuffer(data[end:end + n * PLY_VERTEX_DTYPE.itemsize], dtype=PLY_VERTEX_DTYPE).copy()
+
+
+# ---- a whole scan at once ------------------------------------------------------------------------------------------
+
+SceneTables = collections.namedtuple("SceneTables", "pair_table ref_view ref_mats view_mats")
+SCRATCH_BUDGET = 64 << 20      # bytes of per-call scratch (tables, workgroup counts and offsets) before fuse_scene chunks
+
+
+def scene_tables(pairs, Ks, Es):
+    """pairs [(ref_view, [src_view, ...]), ...] (``formats.read_pair_file``), Ks [V,3,3], Es [V,4,4] -> SceneTables:
+    ``pair_table`` [R,Smax] int32 padded with -1, ``ref_view`` [R] int32, ``ref_mats`` [R,30] float64 = inv(K_ref),
+    K_ref, inv(E_ref)[:3], ``view_mats`` [R,Smax,42] float64 (zeros behind the padding).  Pure NumPy; row r holds the
+    very bits ``view_matrices`` gives for reference view r (float32 products and inverses, widened)."""
+    pairs = [(int(r), [int(v) for v in srcs]) for r, srcs in pairs]
+    V = len(Ks)
+    if len(Es) != V or not pairs:
+        raise RuntimeError("scene_tables: need one K and one E per view and at least one reference view")
+    for r, srcs in pairs:
+        if not srcs:
+            raise RuntimeError("scene_tables: reference view %d has an empty source list" % r)
+        for v in [r] + srcs:
+            if not 0 <= v < V:
+                raise RuntimeError("scene_tables: view index %d lies outside the stack of %d views" % (v, V))
+    R, smax = len(pairs), max(len(srcs) for _, srcs in pairs)
+    pair_table = np.full((R, smax), -1, dtype=np.int32)
+    ref_mats = np.zeros((R, 30), dtype=np.float64)
+    view_mats = np.zeros((R, smax, 42), dtype=np.float64)
+    for i, (r, srcs) in enumerate(pairs):
+        pair_table[i, :len(srcs)] = srcs
+        rm, vm = view_matrices(Ks[r], Es[r], [Ks[v] for v in srcs], [Es[v] for v in srcs])
+        ref_mats[i, :18] = rm
+        ref_mats[i, 18:] = np.linalg.inv(_np32(Es[r]))[:3].reshape(-1)
+        view_mats[i, :len(srcs)] = vm
+    return SceneTables(pair_table, np.array([r for r, _ in pairs], dtype=np.int32), ref_mats, view_mats)
+
+
+class SceneResult(dict):
+    """What ``fuse_scene`` returns: a dict of tensors on the GPU (``points``, ``colors``, ``counts``, ``photo_mask``,
+    ``geo_mask``, ``final_mask``, ``geo_mask_sum``, ``depth_est_averaged``) plus ``vertices()``."""
+
+    def vertices(self):
+        """The structured vertex array of filter_depth (test_mvs4.py:409-418) on the host, ready for ``write_ply``."""
+        pts, cols = self["points"].cpu().numpy(), self["colors"].cpu().numpy()
+        v = np.empty(len(pts), dtype=PLY_VERTEX_DTYPE)
+        v["x"], v["y"], v["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+        v["red"], v["green"], v["blue"] = cols[:, 0], cols[:, 1], cols[:, 2]
+        return v
+
+
+def _scene_stack(x, dev, dtype, what):
+    """Maps of a scan (array, tensor, or a sequence of either) -> one contiguous tensor [V, ...] on ``dev``."""
+    if not isinstance(x, (torch.Tensor, np.ndarray)):
+        x = list(x)
+        if len({tuple(m.shape) for m in x}) > 1:
+            raise RuntimeError("fuse_scene: %s maps of different sizes inside one scan" % what)
+        if all(isinstance(m, torch.Tensor) for m in x):
+            x = torch.stack([m.to(dev) for m in x])
+        else:
+            x = np.stack([m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in x])
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=dtype))
+    return x.to(dev, getattr(torch, np.dtype(dtype).name)).contiguous()
+
+
+def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=1.0, rel_thres=0.01,
+               device=None, scratch_budget=SCRATCH_BUDGET, events=None):
+    """filter_depth (test_mvs4.py:331-421) for a scan whose maps are in memory.  depths / confidences [V,H,W], images
+    [V,H,W,3] (uint8, or float 0..1 as ``read_img`` returns it), Ks [V,3,3], Es [V,4,4]: NumPy arrays, tensors or
+    sequences of them, indexed by the view numbers in ``pairs`` [(ref_view, [src_view, ...]), ...].  Tensors already on
+    the GPU are used as they are.  -> SceneResult (tensors on the GPU): ``points`` [M,3] float32 and ``colors`` [M,3]
+    uint8 in the reference's order (reference views in pair order, pixels row-major), ``counts`` [R] int64 survivors
+    per reference view, ``photo_mask`` / ``geo_mask`` / ``final_mask`` [R,H,W] bool, ``geo_mask_sum`` [R,H,W] int32,
+    ``depth_est_averaged`` [R,H,W] float64.  The only host synchronisation is the read-back of the workgroup offsets
+    at the view boundaries (M and ``counts``), once per call -- once per chunk of reference views when the tables and
+    scan scratch of the whole scan would exceed ``scratch_budget`` bytes; the result does not depend on the chunking.
+    ``events``: a list that receives (name, start, end) torch.cuda.Event triples around the two library calls (timing)."""
+    if device is None:
+        devs = [m.device for x in (depths, confidences, images) for m in ([x] if isinstance(x, torch.Tensor) else
+                                                                          x if not isinstance(x, np.ndarray) else [])
+                if isinstance(m, torch.Tensor) and m.is_cuda]
+        if not devs:
+            raise RuntimeError("mvster_amd.fusion.fuse_scene runs on MI355X only: pass device= or tensors on the GPU "
+                               "(there is no CPU fallback)")
+        device = devs[0]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("mvster_amd.fusion.fuse_scene runs on MI355X only (there is no CPU fallback)")
+    Ks = [_np32(k) for k in Ks]
+    Es = [_np32(e) for e in Es]
+    tables = scene_tables(pairs, Ks, Es)
+    depth = _scene_stack(depths, dev, np.float32, "depth")
+    conf = _scene_stack(confidences, dev, np.float32, "confidence")
+    first = images if isinstance(images, (torch.Tensor, np.ndarray)) else images[0]
+    is_u8 = first.dtype in (torch.uint8, np.dtype(np.uint8))
+    img = _scene_stack(images, dev, np.uint8 if is_u8 else np.float32, "image")
+    if depth.dim() != 3 or conf.shape != depth.shape or tuple(img.shape) != tuple(depth.shape) + (3,):
+        raise RuntimeError("fuse_scene: map sizes differ inside the scan (depth %s, confidence %s, images %s)" %
+                           (tuple(depth.shape), tuple(conf.shape), tuple(img.shape)))
+    V, H, W = depth.shape
+    if V != len(Ks):
+        raise RuntimeError("fuse_scene: %d depth maps for %d cameras" % (V, len(Ks)))
+    R, smax = tables.pair_table.shape
+    lib = _lib.load()
+    nblk = lib.mvster_geo_scene_blocks(1, H, W)
+    _lib.check(min(nblk, 0), "geo_scene_blocks")
+    per_view = nblk * 12 + 8 + smax * (4 + 42 * 8) + 4 + 30 * 8          # counts + offsets + table rows of one view
+    chunk = max(1, min(R, int(scratch_budget) // per_view))
+    mask_sum = torch.empty(R, H, W, device=dev, dtype=torch.int32)
+    avg = torch.empty(R, H, W, device=dev, dtype=torch.float64)
+    photo, geo, final = (torch.empty(R, H, W, device=dev, dtype=torch.bool) for _ in range(3))
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    pts, cols, counts = [], [], []
+    for r0 in range(0, R, chunk):
+        r1 = min(R, r0 + chunk)
+        n = r1 - r0
+        # one upload for the chunk's tables: int32 pair table and view list, then the float64 blocks
+        ints = np.concatenate([tables.pair_table[r0:r1].reshape(-1), tables.ref_view[r0:r1]])
+        if ints.size % 2:
+            ints = np.concatenate([ints, np.zeros(1, np.int32)])
+        host = np.concatenate([ints.view(np.float64), tables.ref_mats[r0:r1].reshape(-1),
+                               tables.view_mats[r0:r1].reshape(-1)])
+        blob = torch.from_numpy(host).to(dev)
+        base = blob.data_ptr()
+        p_pairs, p_ref = base, base + 4 * n * smax
+        p_rm = base + 4 * ints.size
+        p_vm = p_rm + 8 * n * 30
+        wg_counts = torch.empty(n * nblk, device=dev, dtype=torch.int32)
+        wg_offsets = torch.empty(n * nblk + 1, device=dev, dtype=torch.int64)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if events is not None else None
+        if marks:
+            marks[0].record()
+        rc = lib.mvster_geo_scene_filter(depth.data_ptr(), conf.data_ptr(), p_pairs, p_ref, p_rm, p_vm,
+                                         mask_sum[r0:r1].data_ptr(), avg[r0:r1].data_ptr(), photo[r0:r1].data_ptr(),
+                                         geo[r0:r1].data_ptr(), final[r0:r1].data_ptr(), wg_counts.data_ptr(),
+                                         wg_offsets.data_ptr(), n, smax, V, H, W, float(conf_thres), int(thres_view),
+                                         float(pix_thres), float(rel_thres), stream)
+        _lib.check(rc, "geo_scene_filter")
+        if marks:
+            marks[1].record()
+        bounds = wg_offsets[::nblk].cpu()                                   # the one host sync: M and the per-view counts
+        M = int(bounds[-1])
+        counts.append(bounds[1:] - bounds[:-1])
+        points = torch.empty(M, 3, device=dev, dtype=torch.float32)
+        colors = torch.empty(M, 3, device=dev, dtype=torch.uint8)
+        if marks:
+            marks[2].record()
+        rc = lib.mvster_geo_scene_emit(avg[r0:r1].data_ptr(), final[r0:r1].data_ptr(), p_ref, p_rm, img.data_ptr(),
+                                       0 if is_u8 else 1, wg_offsets.data_ptr(), points.data_ptr() if M else None,
+                                       colors.data_ptr() if M else None, M, n, V, H, W, stream)
+        _lib.check(rc, "geo_scene_emit")
+        if marks:
+            marks[3].record()
+            events += [("filter+scan", marks[0], marks[1]), ("emit", marks[2], marks[3])]
+        pts.append(points)
+        cols.append(colors)
+    return SceneResult(points=pts[0] if len(pts) == 1 else torch.cat(pts), colors=cols[0] if len(cols) == 1 else torch.cat(cols),
+                       counts=torch.cat(counts).to(dev), photo_mask=photo, geo_mask=geo, final_mask=final,
+                       geo_mask_sum=mask_sum, depth_est_averaged=avg)
+
+
+def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, thres_view=5, device="cuda:0"):
+    """The reference's ``filter_depth`` (test_mvs4.py:331-421; its ``args.conf`` / ``args.thres_view`` are keywords
+    here): reads ``pair_folder/pair.txt``, ``scan_folder/cams/{:0>8}_cam.txt`` and ``images/{:0>8}.jpg``,
+    ``out_folder/depth_est/{:0>8}.pfm`` and ``confidence/{:0>8}.pfm`` -- every file once --, fuses the scan on the GPU and
+    writes ``out_folder/mask/{:0>8}_{photo,geo,final}.png`` (:390-393) and the point cloud ``plyfilename``.
+    -> the vertex array."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("filter_depth reads the scan's JPEGs and writes its mask PNGs with Pillow (PIL), which is "
+                           "not installed; fuse_scene() on arrays needs no image library") from e
+    pairs = formats.read_pair_file(os.path.join(pair_folder, "pair.txt"))
+    views = sorted({v for r, srcs in pairs for v in [r] + srcs})
+    slot = {v: i for i, v in enumerate(views)}
+    name = "{:0>8}".format
+    cams = [formats.read_camera_parameters(os.path.join(scan_folder, "cams", name(v) + "_cam.txt")) for v in views]
+    depths = [np.asarray(formats.read_pfm(os.path.join(out_folder, "depth_est", name(v) + ".pfm"))[0], np.float32)
+              for v in views]
+    confs = [np.asarray(formats.read_pfm(os.path.join(out_folder, "confidence", name(v) + ".pfm"))[0], np.float32)
+             for v in views]
+    # 8-bit pixels as stored: (read_img's v / 255 * 255) truncated is v again, so the float image is never needed
+    images = [np.array(Image.open(os.path.join(scan_folder, "images", name(v) + ".jpg")), dtype=np.uint8) for v in views]
+    res = fuse_scene(depths, confs, images, [c[0] for c in cams], [c[1] for c in cams],
+                     [(slot[r], [slot[v] for v in srcs]) for r, srcs in pairs], conf, thres_view, device=device)
+    os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+    masks = {k: res[k + "_mask"].cpu().numpy() for k in ("photo", "geo", "final")}
+    for i, (ref_view, _) in enumerate(pairs):
+        for k, m in masks.items():                                          # save_mask: bool -> uint8 * 255
+            Image.fromarray(m[i].astype(np.uint8) * 255).save(os.path.join(out_folder, "mask", name(ref_view) + "_%s.png" % k))
+    vertices = res.vertices()
+    write_ply(plyfilename, vertices)
+    return vertices
