@@ -38,6 +38,11 @@ int mvster_relative_projection_multi(const float* const* proj_matrices, int nsta
  * out [N*B,H,W,4] channels-last RGB0, view-major: the batch FPN4 runs on. */
 int mvster_pack_images(const float* const* imgs, int N, float* out, int B, int H, int W, void* stream);
 
+/* imgs uint8 [V,H,W,3] (what an image file decodes to; 4-byte aligned) -> out [V,1,H,W,4] float RGB0, value u8 / 255 with a
+ * true division: the bits of read_img (datasets/general_eval4.py:81-86) followed by mvster_pack_images, for a whole scan in
+ * one launch and from a quarter of the bytes. */
+int mvster_pack_images_u8(const unsigned char* imgs, float* out, int V, int H, int W, void* stream);
+
 /* The three launches a forward starts with in one (MVS4Net.py:60-76): mvster_pack_images (imgs -> packed),
  * mvster_relative_projection_multi (proj_matrices -> rt) and mvster_init_range (depth_values [B,ndv] -> hypo [B,D,h,w], the
  * first stage's hypotheses; h*w <= H*W).  Same arithmetic as the three, bit for bit. */
@@ -58,6 +63,23 @@ int mvster_warp_agg_fwd(const float* ref_feat, const float* src_feat, const floa
                         float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w, int Hs,
                         int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride, int group_cor,
                         int attn_fuse_d, float attn_temp, int variant, void* stream);
+
+/* mvster_warp_agg_fwd reading its maps by index from a LEVEL STORE [V,h,w,C] (one pyramid level of every view of a scan):
+ * the reference map of batch item b is map views[b][0] of the store and its NV source maps are views[b][1..NV]; `views`
+ * is a DEVICE int32 table [B,1+NV] (a captured graph is replayed for another reference view after updating the table).
+ * Repeated indices are legal.  Same kernels (one template parameter apart: how a view's base address is formed), same
+ * (C, G, D, group_cor, attn_fuse_d, variant 0..3) combinations and the same bits as mvster_warp_agg_fwd on a gathered
+ * copy.  The indices are NOT checked on the device: the caller validates 0 <= index < V before uploading them.
+ * MVSTER_ERR_UNSUPPORTED (-3) where the plain entry returns it, and for the kernel forms whose indexed instantiation would
+ * leave the plain one's register budget class (one thread per (pixel, d) at C = 16; the lane-split form at (C, G) = (16, 8)
+ * and (64, 8) -- none of them in the shipped cascade): mvster_gather_views + mvster_warp_agg_fwd there. */
+int mvster_warp_agg_fwd_indexed(const float* store, const int* views, const float* rt, const float* hypo, float* out,
+                                float* wsum_out, int V, int B, int NV, int C, int G, int D, int h, int w, int group_cor,
+                                int attn_fuse_d, float attn_temp, int variant, void* stream);
+
+/* Maps views[b][k] (DEVICE int32 table [B,N], unchecked) of a level store [V, map_floats] -> out [N,B,map_floats]: the
+ * view-major batch mvster_warp_agg_fwd reads (ref_feat = out, src_feat = out + B*map_floats).  map_floats % 4 == 0. */
+int mvster_gather_views(const float* store, const int* views, float* out, int V, int B, int N, long map_floats, void* stream);
 
 /* mvster_warp_agg_fwd with the stage's depth-hypothesis scheduling fused in: one launch instead of
  * (mvster_schedule_inverse_range | mvster_init_range) + mvster_warp_agg_fwd.  mode 1: the hypotheses are

@@ -2,10 +2,14 @@
 
 Public surface = the reference's ``models`` package surface (models/__init__.py:2):
 ``MVS4net``, ``MVS4net_loss``, ``Blend_loss``; plus the fusion step of its test script (test_mvs4.py:331-421):
-``filter_depth`` for a scan on disk, ``fuse_scene`` / ``scene_tables`` for one in memory.
+``filter_depth`` for a scan on disk, ``fuse_scene`` / ``scene_tables`` for one in memory; and the loop before it
+(``save_scene_depth``, :170-268) at the level of a scan: ``infer_scan`` / ``infer_scan_folder`` (FPN once per image, all
+depth maps of a scan on the GPU), ``write_scan_outputs``, ``reconstruct_scan`` (inference + fusion without leaving the GPU).
 """
 from .fusion import filter_depth, fuse_scene, scene_tables
 from .loss import Blend_loss, MVS4net_loss
 from .net import MVS4net
+from .scan import infer_scan, infer_scan_folder, reconstruct_scan, write_scan_outputs
 
-__all__ = ["MVS4net", "MVS4net_loss", "Blend_loss", "filter_depth", "fuse_scene", "scene_tables"]
+__all__ = ["MVS4net", "MVS4net_loss", "Blend_loss", "filter_depth", "fuse_scene", "scene_tables",
+           "infer_scan", "infer_scan_folder", "reconstruct_scan", "write_scan_outputs"]

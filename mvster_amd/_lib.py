@@ -21,8 +21,11 @@ SIGNATURES = {
     "mvster_relative_projection": [_f, _f, _i, _i, _f],
     "mvster_relative_projection_multi": [_f, _i, _f, _i, _i, _f],
     "mvster_pack_images": [_f, _i, _f, _i, _i, _i, _f],
+    "mvster_pack_images_u8": [_f, _f, _i, _i, _i, _f],
     "mvster_forward_prologue": [_f, _i, _f, _i, _i, _i, _f, _i, _f, _f, _i, _f, _i, _i, _i, _i, _f],
     "mvster_warp_agg_fwd": [_f, _f, _f, _f, _f, _f] + [_i] * 9 + [_l] * 3 + [_i, _i, _fl, _i, _f],
+    "mvster_warp_agg_fwd_indexed": [_f, _f, _f, _f, _f, _f] + [_i] * 10 + [_fl, _i, _f],
+    "mvster_gather_views": [_f, _f, _f, _i, _i, _i, _l, _f],
     "mvster_warp_agg_fwd_sched": [_f] * 6 + [_i, _f, _f, _f] + [_i] * 9 + [_l] * 3 + [_i, _fl, _i, _f],
     "mvster_warp_agg_bwd": [_f] * 11 + [_i] * 9 + [_l] * 3 + [_i, _i, _fl, _f],
     "mvster_warp_agg_bwd_scratch": [_i] * 8 + [_f, _f],

@@ -818,6 +818,30 @@ __global__ void pack_images_kernel(PackArgs a) {
     st4(a.out + ((long)vb * a.HW + p) * 4, px);
 }
 
+// 8-bit images [n pixels, 3] (what a JPEG decodes to) -> RGB0 float [n, 4], value u8 / 255 with a true division: the bits of
+// read_img (general_eval4.py:81-86, float32(u8) / float32(255)) followed by pack_images.  A thread converts four pixels:
+// three aligned 32-bit loads, four 16-byte stores.
+__global__ void __launch_bounds__(256) pack_images_u8_kernel(const unsigned char* __restrict__ src, float* __restrict__ out, long n) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;      // group of four pixels
+    const long p0 = q * 4;
+    if (p0 >= n) return;
+    if (p0 + 4 <= n) {
+        const unsigned* w = reinterpret_cast<const unsigned*>(src + p0 * 3);   // 12 bytes per group: 4-byte aligned
+        const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+        const unsigned char by[12] = {(unsigned char)w0, (unsigned char)(w0 >> 8), (unsigned char)(w0 >> 16), (unsigned char)(w0 >> 24),
+                                      (unsigned char)w1, (unsigned char)(w1 >> 8), (unsigned char)(w1 >> 16), (unsigned char)(w1 >> 24),
+                                      (unsigned char)w2, (unsigned char)(w2 >> 8), (unsigned char)(w2 >> 16), (unsigned char)(w2 >> 24)};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            st4(out + (p0 + k) * 4, (f32x4){mv::div_rn((float)by[3 * k], 255.0f), mv::div_rn((float)by[3 * k + 1], 255.0f),
+                                            mv::div_rn((float)by[3 * k + 2], 255.0f), 0.0f});
+    } else {
+        for (long p = p0; p < n; ++p)
+            st4(out + p * 4, (f32x4){mv::div_rn((float)src[p * 3], 255.0f), mv::div_rn((float)src[p * 3 + 1], 255.0f),
+                                     mv::div_rn((float)src[p * 3 + 2], 255.0f), 0.0f});
+    }
+}
+
 struct MultiProjArgs {
     const float* pm[8];     // per stage [B,N,2,4,4]
     float* rt;              // [nstage, B, N-1, 12]
@@ -1108,6 +1132,15 @@ extern "C" int mvster_pack_images(const float* const* imgs, int N, float* out, i
     }
     a.out = out; a.N = N; a.B = B; a.HW = H * W;
     hipLaunchKernelGGL(pack_images_kernel, dim3((H * W + 255) / 256, N * B), dim3(256), 0, (hipStream_t)stream, a);
+    return mv_check_launch();
+}
+
+extern "C" int mvster_pack_images_u8(const unsigned char* imgs, float* out, int V, int H, int W, void* stream) {
+    if (!imgs || !out) return MVSTER_ERR_NULL;
+    if (V <= 0 || H <= 0 || W <= 0 || ((uintptr_t)imgs & 3)) return MVSTER_ERR_SHAPE;
+    const long n = (long)V * H * W, groups = (n + 3) / 4;
+    if ((groups + 255) / 256 > 0x7fffffffL) return MVSTER_ERR_SHAPE;
+    hipLaunchKernelGGL(pack_images_u8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, imgs, out, n);
     return mv_check_launch();
 }
 

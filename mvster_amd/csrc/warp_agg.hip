@@ -52,11 +52,37 @@ struct WarpAggArgs {
     const float* dvals;      // SCHED 2: depth_values [B, ndv] (first and last column = the range)
     float* hypo_out;
     int ndv;
+    // indexed form (mvster_warp_agg_fwd_indexed): ref = src = a level store [V, h, w, C] holding every view of a scan, and
+    // batch item b reads maps views[b * (1 + NV) + 0] (reference) and [.. + 1 + v] (source v) of it
+    const int* views;        // DEVICE table [B, 1 + NV]; nullptr in the plain forms
+    long store_vs;           // view stride of the store (elements)
 };
+
+// Base address of a view's map: the ONLY difference between the plain and the indexed launch forms.  The table entry is
+// uniform over the workgroup (b = blockIdx.y, v = the loop counter), i.e. one scalar load per view.
+template <bool IDX>
+__device__ __forceinline__ const float* ref_base(const WarpAggArgs& a, int b) {
+    if constexpr (IDX) return a.ref + (long)a.views[b * (a.NV + 1)] * a.store_vs;
+    else return a.ref + (long)b * a.ref_bs;
+}
+template <bool IDX>
+__device__ __forceinline__ const float* src_base(const WarpAggArgs& a, int b, int v) {
+    if constexpr (IDX) return a.src + (long)a.views[b * (a.NV + 1) + 1 + v] * a.store_vs;
+    else return a.src + (long)v * a.src_vs + (long)b * a.src_bs;
+}
+
+// Forms whose INDEXED instantiation leaves the register budget class of the plain one (compiler's counts, gfx950, -O3:
+// one-thread form at C = 16: 72-80 -> 84-106 VGPRs, 6-7 -> 4-5 waves per SIMD; lane-split form at (16, 8) and (64, 8):
+// 71 / 67 -> 79 / 73 VGPRs, 7 -> 6 waves).  They are not instantiated: the indexed entry answers MVSTER_ERR_UNSUPPORTED and
+// the caller gathers the maps (mvster_gather_views) for the plain entry.  None of them is a kernel of the shipped cascade.
+template <int C>
+constexpr bool kIndexedOneThread = C != 16;
+template <int C, int G>
+constexpr bool kIndexedLanes = !((C == 16 && G == 8) || (C == 64 && G == 8));
 
 // PX pixels x D hypotheses per workgroup: 64 pixels for D <= 16 (the shipped cascade's fallback form), 32 / 16 pixels for up
 // to 32 / 64 hypotheses per stage (free --ndepths of the reference; evaluation only, the backward keeps D <= 16).
-template <int C, int G, bool GROUP, int DMAX, int PX = 64>
+template <int C, int G, bool GROUP, int DMAX, int PX = 64, bool IDX = false>
 __global__ void __launch_bounds__(PX * DMAX) warp_agg_fwd_kernel(WarpAggArgs a) {
     static_assert(C % 8 == 0, "channels-last taps are read as float4 pairs");
     static_assert(GROUP ? (C % G == 0) : (C == G), "group layout");
@@ -80,7 +106,7 @@ __global__ void __launch_bounds__(PX * DMAX) warp_agg_fwd_kernel(WarpAggArgs a) 
     const int y = pc / a.w;
     const int x = pc - y * a.w;
     const float depth = a.hypo[((long)b * a.D + d) * hw + pc];
-    const float* rp = a.ref + (long)b * a.ref_bs + (long)pc * C;
+    const float* rp = ref_base<IDX>(a, b) + (long)pc * C;
 
     float acc[G];
 #pragma unroll
@@ -100,7 +126,7 @@ __global__ void __launch_bounds__(PX * DMAX) warp_agg_fwd_kernel(WarpAggArgs a) 
         mv::project(m, (float)x, (float)y, depth, a.Hs, a.Ws, sx, sy);
         mv::Taps t = mv::make_taps(sx, sy, a.Hs, a.Ws);
         const mv::TapsClamped tc = mv::clamp_taps(t, a.Hs, a.Ws);
-        const float* sp = a.src + (long)v * a.src_vs + (long)b * a.src_bs;
+        const float* sp = src_base<IDX>(a, b, v);
         const float* p00 = sp + ((long)tc.ya * a.Ws + tc.xa) * C;
         const float* p01 = sp + ((long)tc.ya * a.Ws + tc.xb) * C;
         const float* p10 = sp + ((long)tc.yb * a.Ws + tc.xa) * C;
@@ -182,7 +208,7 @@ __global__ void __launch_bounds__(PX * DMAX) warp_agg_fwd_kernel(WarpAggArgs a) 
 // waves, and there is a single gather round per view.  The G correlations are all-gathered with wave
 // shuffles and summed in group order, so scores are bit-identical to the one-thread form.
 // ------------------------------------------------------------------------------------------
-template <int C, int G, int DMAX>
+template <int C, int G, int DMAX, bool IDX = false>
 __global__ void __launch_bounds__(64 * DMAX) warp_agg_fwd_lanes_kernel(WarpAggArgs a) {
     constexpr int LPP = C / 8;           // lanes per (pixel, d)
     constexpr int CG = C / G;            // channels per group
@@ -202,7 +228,7 @@ __global__ void __launch_bounds__(64 * DMAX) warp_agg_fwd_lanes_kernel(WarpAggAr
     const int y = pc / a.w;
     const int x = pc - y * a.w;
     const float depth = a.hypo[((long)b * a.D + d) * hw + pc];
-    const float* rp = a.ref + (long)b * a.ref_bs + (long)pc * C + sub * 8;
+    const float* rp = ref_base<IDX>(a, b) + (long)pc * C + sub * 8;
     const f32x4 R0 = ld4(rp), R1 = ld4(rp + 4);
 
     float acc[GPL];
@@ -223,7 +249,7 @@ __global__ void __launch_bounds__(64 * DMAX) warp_agg_fwd_lanes_kernel(WarpAggAr
         mv::project(m, (float)x, (float)y, depth, a.Hs, a.Ws, sx, sy);
         mv::Taps t = mv::make_taps(sx, sy, a.Hs, a.Ws);
         const mv::TapsClamped tc = mv::clamp_taps(t, a.Hs, a.Ws);
-        const float* sp = a.src + (long)v * a.src_vs + (long)b * a.src_bs + sub * 8;
+        const float* sp = src_base<IDX>(a, b, v) + sub * 8;
         const float* p00 = sp + ((long)tc.ya * a.Ws + tc.xa) * C;
         const float* p01 = sp + ((long)tc.ya * a.Ws + tc.xb) * C;
         const float* p10 = sp + ((long)tc.yb * a.Ws + tc.xa) * C;
@@ -296,7 +322,7 @@ __global__ void __launch_bounds__(64 * DMAX) warp_agg_fwd_lanes_kernel(WarpAggAr
 // 2 = init_inverse_range of depth_values, both computed per lane with the scheduler kernels' own per-hypothesis functions
 // (mvster_math.h: bit-identical) and written to a.hypo_out by lane sub 0 -- one launch and one dependency edge less per
 // stage (schedule_inverse_kernel ran alone for ~5 us three times per forward).
-template <int C, int G, int D, int SCHED = 0>
+template <int C, int G, int D, int SCHED = 0, bool IDX = false>
 __global__ void __launch_bounds__(256) warp_agg_fwd_wave_kernel(WarpAggArgs a) {
     constexpr int LPP = C / 8;           // lanes per (pixel, d)
     constexpr int CG = C / G;            // channels per group
@@ -327,7 +353,7 @@ __global__ void __launch_bounds__(256) warp_agg_fwd_wave_kernel(WarpAggArgs a) {
         }
         if (valid && sub == 0) a.hypo_out[((long)b * D + d) * hw + pc] = depth;
     }
-    const float* rp = a.ref + (long)b * a.ref_bs + (long)pc * C + sub * 8;
+    const float* rp = ref_base<IDX>(a, b) + (long)pc * C + sub * 8;
     const f32x4 R0 = ld4(rp), R1 = ld4(rp + 4);
     // per-launch divisors with their reciprocals (mvster_math.h: same bits as '/', 5 instead of 11 VALU ops)
     const mv::GridNorm gn = mv::make_grid_norm(a.Hs, a.Ws);
@@ -371,7 +397,7 @@ __global__ void __launch_bounds__(256) warp_agg_fwd_wave_kernel(WarpAggArgs a) {
         // addresses are immediate offsets; nothing is clamped -- a tap outside the map either falls outside the
         // descriptor (the hardware returns 0) or reads some other texel, and its weight is 0 in both cases
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(a.src + (long)v * a.src_vs + (long)b * a.src_bs), (short)0, (int)src_bytes, 0x00020000);
+            const_cast<float*>(src_base<IDX>(a, b, v)), (short)0, (int)src_bytes, 0x00020000);
         const unsigned oa = (((unsigned)__mul24(t.y0, a.Ws) + (unsigned)t.x0) << SH) + (unsigned)(sub * 32);
         const unsigned ob = oa + (unsigned)row_bytes;
         const f32x4 q0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, oa, 0, 0));
@@ -724,6 +750,9 @@ int launch_fwd_wave(const WarpAggArgs& a, hipStream_t stream, int sched = 0) {
     } else if (sched == 2) {
         MV_NOTE_KERNEL("warp_agg_fwd_wave_kernel<%d, %d, %d, 2>", C, G, D);
         hipLaunchKernelGGL((warp_agg_fwd_wave_kernel<C, G, D, 2>), grid, dim3(256), 0, stream, a);
+    } else if (a.views) {
+        MV_NOTE_KERNEL("warp_agg_fwd_wave_kernel<%d, %d, %d, 0, true>", C, G, D);
+        hipLaunchKernelGGL((warp_agg_fwd_wave_kernel<C, G, D, 0, true>), grid, dim3(256), 0, stream, a);
     } else {
         MV_NOTE_KERNEL("warp_agg_fwd_wave_kernel<%d, %d, %d>", C, G, D);
         hipLaunchKernelGGL((warp_agg_fwd_wave_kernel<C, G, D>), grid, dim3(256), 0, stream, a);
@@ -989,32 +1018,62 @@ int launch_fwd_lanes(const WarpAggArgs& a, hipStream_t stream) {
     if (a.D > 8) return MVSTER_ERR_UNSUPPORTED;
     dim3 block(64, a.D);
     dim3 grid((a.h * a.w + PPB - 1) / PPB, a.B);
-    MV_NOTE_KERNEL("warp_agg_fwd_lanes_kernel<%d, %d, 8>", C, G);
-    hipLaunchKernelGGL((warp_agg_fwd_lanes_kernel<C, G, 8>), grid, block, 0, stream, a);
+    if (a.views) {
+        if constexpr (kIndexedLanes<C, G>) {
+            MV_NOTE_KERNEL("warp_agg_fwd_lanes_kernel<%d, %d, 8, true>", C, G);
+            hipLaunchKernelGGL((warp_agg_fwd_lanes_kernel<C, G, 8, true>), grid, block, 0, stream, a);
+        } else {
+            return MVSTER_ERR_UNSUPPORTED;
+        }
+    } else {
+        MV_NOTE_KERNEL("warp_agg_fwd_lanes_kernel<%d, %d, 8>", C, G);
+        hipLaunchKernelGGL((warp_agg_fwd_lanes_kernel<C, G, 8>), grid, block, 0, stream, a);
+    }
     return mv_check_launch();
+}
+
+// plain or indexed instantiation of the one-thread form (mvster_last_kernel reports the plain spelling for both)
+template <int C, int G, bool GROUP, int DMAX, int PX>
+void launch_fwd_form(const WarpAggArgs& a, dim3 grid, dim3 block, hipStream_t stream) {
+    if constexpr (kIndexedOneThread<C>) {
+        if (a.views) {
+            hipLaunchKernelGGL((warp_agg_fwd_kernel<C, G, GROUP, DMAX, PX, true>), grid, block, 0, stream, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((warp_agg_fwd_kernel<C, G, GROUP, DMAX, PX>), grid, block, 0, stream, a);
+}
+
+// maps views[b][k] of a level store -> out [1 + NV, B, map]: the view-major batch the plain entry reads (16 bytes per thread)
+__global__ void __launch_bounds__(256) gather_views_kernel(const float* __restrict__ store, const int* __restrict__ views,
+                                                          float* __restrict__ out, int B, int N, long map_quads) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= map_quads) return;
+    const int k = blockIdx.y / B, b = blockIdx.y - k * B;            // out map k * B + b
+    const long src = (long)views[b * N + k] * map_quads + q, dst = (long)blockIdx.y * map_quads + q;
+    st4(out + dst * 4, ld4(store + src * 4));
 }
 
 template <int C, int G, bool GROUP>
 int launch_fwd(const WarpAggArgs& a, hipStream_t stream) {
     dim3 block(64, a.D);
     dim3 grid((a.h * a.w + 63) / 64, a.B);
+    if (a.views && !kIndexedOneThread<C>) return MVSTER_ERR_UNSUPPORTED;
     if (a.D <= 8) {
         MV_NOTE_KERNEL("warp_agg_fwd_kernel<%d, %d, %s, 8>", C, G, GROUP ? "true" : "false");
-        hipLaunchKernelGGL((warp_agg_fwd_kernel<C, G, GROUP, 8>), grid, block, 0, stream, a);
+        launch_fwd_form<C, G, GROUP, 8, 64>(a, grid, block, stream);
     } else {
         // 1024-thread blocks; the per-thread correlations of the widest ungrouped case do not fit LDS
         if constexpr (G * kMaxD * 64 * 4 > 120 * 1024) return MVSTER_ERR_UNSUPPORTED;
         else if (a.D <= kMaxD) {
             MV_NOTE_KERNEL("warp_agg_fwd_kernel<%d, %d, %s, %d>", C, G, GROUP ? "true" : "false", kMaxD);
-            hipLaunchKernelGGL((warp_agg_fwd_kernel<C, G, GROUP, kMaxD>), grid, block, 0, stream, a);
+            launch_fwd_form<C, G, GROUP, kMaxD, 64>(a, grid, block, stream);
         } else if (a.D <= 32) {          // the same 1024 threads as 32 pixels x 32 hypotheses
             MV_NOTE_KERNEL("warp_agg_fwd_kernel<%d, %d, %s, 32, 32>", C, G, GROUP ? "true" : "false");
-            hipLaunchKernelGGL((warp_agg_fwd_kernel<C, G, GROUP, 32, 32>), dim3((a.h * a.w + 31) / 32, a.B), dim3(32, a.D), 0,
-                               stream, a);
+            launch_fwd_form<C, G, GROUP, 32, 32>(a, dim3((a.h * a.w + 31) / 32, a.B), dim3(32, a.D), stream);
         } else {                         // ... 16 pixels x 64 hypotheses
             MV_NOTE_KERNEL("warp_agg_fwd_kernel<%d, %d, %s, 64, 16>", C, G, GROUP ? "true" : "false");
-            hipLaunchKernelGGL((warp_agg_fwd_kernel<C, G, GROUP, 64, 16>), dim3((a.h * a.w + 15) / 16, a.B), dim3(16, a.D), 0,
-                               stream, a);
+            launch_fwd_form<C, G, GROUP, 64, 16>(a, dim3((a.h * a.w + 15) / 16, a.B), dim3(16, a.D), stream);
         }
     }
     return mv_check_launch();
@@ -2120,7 +2179,7 @@ extern "C" int mvster_warp_agg_fwd_sched(const float* ref_feat, const float* src
     if (D != 4 && D != 8) return MVSTER_ERR_UNSUPPORTED;
     WarpAggArgs a;
     a.ref = ref_feat; a.src = src_feat; a.rt = rt; a.hypo = nullptr; a.out = out; a.wsum_out = wsum_out;
-    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride;
+    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride; a.views = nullptr; a.store_vs = 0;
     a.B = B; a.NV = NV; a.D = D; a.h = h; a.w = w; a.Hs = Hs; a.Ws = Ws;
     a.attn_temp = attn_temp; a.sqrt_c = sqrtf((float)C); a.fuse_d = attn_fuse_d;
     a.inv_min = inv_min; a.inv_max = inv_max; a.dvals = depth_values; a.hypo_out = hypo_out; a.ndv = ndv;
@@ -2132,25 +2191,30 @@ extern "C" int mvster_warp_agg_fwd_sched(const float* ref_feat, const float* src
     return MVSTER_ERR_UNSUPPORTED;
 }
 
-extern "C" int mvster_warp_agg_fwd(const float* ref_feat, const float* src_feat, const float* rt, const float* hypo,
-                                   float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w,
-                                   int Hs, int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride,
-                                   int group_cor, int attn_fuse_d, float attn_temp, int variant, void* stream) {
+// the forward's argument checks and kernel choice, shared by the plain and the indexed entry (views != nullptr: ref_feat =
+// src_feat = the level store, view stride store_vs, and the three plain strides are unused)
+static int warp_agg_fwd_any(const float* ref_feat, const float* src_feat, const float* rt, const float* hypo,
+                            float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w,
+                            int Hs, int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride,
+                            int group_cor, int attn_fuse_d, float attn_temp, int variant, const int* views, long store_vs,
+                            void* stream) {
     if (!ref_feat || !src_feat || !rt || !hypo || !out) return MVSTER_ERR_NULL;
     if (B <= 0 || NV <= 0 || D <= 0 || D > kMaxFwdD || h <= 0 || w <= 0 || Hs <= 0 || Ws <= 0) return MVSTER_ERR_SHAPE;
     if (!group_cor && G != C) return MVSTER_ERR_SHAPE;
     WarpAggArgs a;
     a.ref = ref_feat; a.src = src_feat; a.rt = rt; a.hypo = hypo; a.out = out; a.wsum_out = wsum_out;
-    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride;
+    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride; a.views = nullptr; a.store_vs = 0;
     a.B = B; a.NV = NV; a.D = D; a.h = h; a.w = w; a.Hs = Hs; a.Ws = Ws;
     a.attn_temp = attn_temp; a.sqrt_c = sqrtf((float)C); a.fuse_d = attn_fuse_d;
     a.inv_min = a.inv_max = a.dvals = nullptr; a.hypo_out = nullptr; a.ndv = 0;
+    a.views = views; a.store_vs = store_vs;
     hipStream_t s = (hipStream_t)stream;
+    if (views && (variant == 4 || variant == 5)) return MVSTER_ERR_UNSUPPORTED;   // (forms kept for the record: plain only)
     // variant: 0 = choose; 1 = one thread per (pixel, d); 2 = workgroup-level lane split (C >= 16);
     // 3 = wave-local kernel (what 0 picks whenever it applies); 4 = pixel-major kernel (faster on cache-resident inputs,
     // slower inside the forward: kept as a tested alternative)
 #ifdef MVSTER_PROBES
-    if (group_cor && (D == 4 || D == 8) && (variant == 4 || (variant == 0 && C <= 16 && g_pix))) {
+    if (!views && group_cor && (D == 4 || D == 8) && (variant == 4 || (variant == 0 && C <= 16 && g_pix))) {
         int rc = MVSTER_ERR_UNSUPPORTED;
         if (C == 8 && G == 4) rc = dispatch_fwd_pix<8, 4>(a, s);
         else if (C == 8 && G == 8) rc = dispatch_fwd_pix<8, 8>(a, s);
@@ -2204,6 +2268,38 @@ extern "C" int mvster_warp_agg_fwd(const float* ref_feat, const float* src_feat,
     return MVSTER_ERR_UNSUPPORTED;
 }
 
+extern "C" int mvster_warp_agg_fwd(const float* ref_feat, const float* src_feat, const float* rt, const float* hypo,
+                                   float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w,
+                                   int Hs, int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride,
+                                   int group_cor, int attn_fuse_d, float attn_temp, int variant, void* stream) {
+    return warp_agg_fwd_any(ref_feat, src_feat, rt, hypo, out, wsum_out, B, NV, C, G, D, h, w, Hs, Ws, ref_batch_stride,
+                            src_view_stride, src_batch_stride, group_cor, attn_fuse_d, attn_temp, variant, nullptr, 0, stream);
+}
+
+// mvster_warp_agg_fwd reading its maps from a level store [V, h, w, C] through a DEVICE table views [B, 1 + NV] (column 0
+// = the reference view); same kernels, same bits as the plain entry on a gathered copy.  The indices are NOT checked here
+// (they are on the device): the caller validates 0 <= index < V before it uploads them.  MVSTER_ERR_UNSUPPORTED also for the
+// forms listed at kIndexedOneThread / kIndexedLanes: gather (mvster_gather_views) and call the plain entry.
+extern "C" int mvster_warp_agg_fwd_indexed(const float* store, const int* views, const float* rt, const float* hypo, float* out,
+                                           float* wsum_out, int V, int B, int NV, int C, int G, int D, int h, int w,
+                                           int group_cor, int attn_fuse_d, float attn_temp, int variant, void* stream) {
+    if (!store || !views) return MVSTER_ERR_NULL;
+    if (V <= 0 || C <= 0) return MVSTER_ERR_SHAPE;
+    return warp_agg_fwd_any(store, store, rt, hypo, out, wsum_out, B, NV, C, G, D, h, w, h, w, 0, 0, 0, group_cor, attn_fuse_d,
+                            attn_temp, variant, views, (long)h * w * C, stream);
+}
+
+extern "C" int mvster_gather_views(const float* store, const int* views, float* out, int V, int B, int N, long map_floats,
+                                   void* stream) {
+    if (!store || !views || !out) return MVSTER_ERR_NULL;
+    if (V <= 0 || B <= 0 || N <= 0 || map_floats <= 0 || map_floats % 4 || (long)B * N > 65535) return MVSTER_ERR_SHAPE;
+    const long quads = map_floats / 4, blocks = (quads + 255) / 256;
+    if (blocks > 0x7fffffffL) return MVSTER_ERR_SHAPE;
+    hipLaunchKernelGGL(gather_views_kernel, dim3((unsigned)blocks, B * N), dim3(256), 0, (hipStream_t)stream, store, views, out, B, N,
+                       quads);
+    return mv_check_launch();
+}
+
 extern "C" int mvster_warp_agg_bwd_scratch(int B, int NV, int C, int G, int D, int h, int w, int attn_fuse_d,
                                           long* window_floats, long* origin_ints);   // (defined below, used by the launcher)
 
@@ -2231,7 +2327,7 @@ extern "C" int mvster_warp_agg_bwd(const float* ref_feat, const float* src_feat,
     WarpAggBwdArgs ba;
     WarpAggArgs& a = ba.f;
     a.ref = ref_feat; a.src = src_feat; a.rt = rt; a.hypo = hypo; a.out = nullptr; a.wsum_out = nullptr;
-    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride;
+    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride; a.views = nullptr; a.store_vs = 0;
     a.B = B; a.NV = NV; a.D = D; a.h = h; a.w = w; a.Hs = Hs; a.Ws = Ws;
     a.attn_temp = attn_temp; a.sqrt_c = sqrtf((float)C); a.fuse_d = attn_fuse_d;
     ba.fwd_out = out; ba.wsum = wsum; ba.grad_out = grad_out; ba.grad_ref = grad_ref; ba.grad_src = grad_src;
@@ -2324,7 +2420,7 @@ extern "C" int mvster_warp_agg_bwd_sorted(const float* ref_feat, const float* sr
     WarpAggBwdArgs ba;
     WarpAggArgs& a = ba.f;
     a.ref = ref_feat; a.src = src_feat; a.rt = rt; a.hypo = hypo; a.out = nullptr; a.wsum_out = nullptr;
-    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride;
+    a.ref_bs = ref_batch_stride; a.src_vs = src_view_stride; a.src_bs = src_batch_stride; a.views = nullptr; a.store_vs = 0;
     a.B = B; a.NV = NV; a.D = D; a.h = h; a.w = w; a.Hs = Hs; a.Ws = Ws;
     a.attn_temp = attn_temp; a.sqrt_c = sqrtf((float)C); a.fuse_d = attn_fuse_d;
     ba.fwd_out = out; ba.wsum = wsum; ba.grad_out = grad_out; ba.grad_ref = grad_ref; ba.grad_src = grad_src;

@@ -344,27 +344,45 @@ class MVS4net(nn.Module):
             o1, o2 = fpn.coarse(c3, f1)
             # a 1- or 2-stage cascade (BASELINE config 1) never reads the two fine levels
             o3, o4 = fpn.tail(c0, c1, f1) if self.num_stage > 2 else (None, None)
-        pyramid = [o1, o2, o3, o4]
-
-        outputs = {}
-        prev = None
-        for s in range(self.num_stage):
-            name = "stage%d" % (s + 1)
-            if s == 2 and side is not None:
+        join = None
+        if side is not None:
+            def join():
                 main.wait_stream(side)                                           # join: stage 3 reads o3, stage 4 o4
                 if not torch.cuda.is_current_stream_capturing():
                     for t in (o3, o4):
                         t.record_stream(main)                                    # allocated on `side`, consumed on `main`
+        return self._cascade_eval([o1, o2, o3, o4], regs, N, B, H, W, rts, depth_values, depth_interval, hypo0=hypo0,
+                                  teacher=teacher, capture=capture, join=join)
+
+    @torch.no_grad()
+    def _cascade_eval(self, pyramid, regs, N, B, H, W, rts, depth_values, depth_interval, hypo0=None, teacher=None,
+                      capture=None, join=None, views=None):
+        """The cascade after the FPN, shared by the per-sample forward and the scan runner (``mvster_amd.scan``).
+        ``pyramid[s]`` is the level stage ``s`` reads: the view-major batch [N*B,1,h,w,C] of ONE sample (``views`` None), or
+        the level STORE [V,h,w,C] of a whole scan with ``views`` the device int32 table [B,N] of the sample's view numbers
+        (column 0 = the reference view) -- the warp kernel then reads the maps by index and everything else is the same
+        launches on the same operands.  ``join``: called before stage 3 (the fine FPN levels' stream).  The store form has
+        no ``mono_feat`` entries (they are views of the per-sample pyramid) and no ``feats_cl`` capture."""
+        outputs = {}
+        prev = None
+        for s in range(self.num_stage):
+            name = "stage%d" % (s + 1)
+            if s == 2 and join is not None:
+                join()
             f = pyramid[s]
-            h, w, C = f.shape[2], f.shape[3], f.shape[4]
-            f = f.view(N, B, h, w, C)
-            ref_cl, src_cl = f[0], f[1:]
+            if views is None:
+                h, w, C = f.shape[2], f.shape[3], f.shape[4]
+                f = f.view(N, B, h, w, C)
+                ref_cl, src_cl = f[0], f[1:]
+            else:
+                h, w, C = f.shape[1], f.shape[2], f.shape[3]
+                ref_cl = src_cl = None
             G = self.group_cor_dim[s] if self.group_cor else C
             rt = rts[s]
             cor = hypo = None
             if teacher is not None and name in teacher:
                 hypo = teacher[name].contiguous()
-            elif self.inverse_depth and self.group_cor and self.warp_variant == 0 and self.fuse_hypotheses:
+            elif views is None and self.inverse_depth and self.group_cor and self.warp_variant == 0 and self.fuse_hypotheses:
                 # the stage's hypotheses are computed inside the warp launch (one kernel and one dependency edge less per stage)
                 fused = ops.warp_agg_fwd_sched_cl(
                     ref_cl.contiguous(), src_cl.contiguous(), rt, G, self.stage_splits[s], self.attn_fuse_d, float(self.attn_temp),
@@ -376,7 +394,10 @@ class MVS4net(nn.Module):
                 hypo = hypo0
             if hypo is None:
                 hypo = self._hypotheses(s, depth_values, depth_interval, prev, h, w)
-            if cor is None:
+            if cor is None and views is not None:
+                cor = ops.warp_agg_fwd_indexed_cl(f, views, rt, hypo, G, self.group_cor, self.attn_fuse_d,
+                                                  float(self.attn_temp), variant=self.warp_variant)
+            elif cor is None:
                 cor = ops.warp_agg_fwd_cl(ref_cl, src_cl, rt, hypo, G, self.group_cor, self.attn_fuse_d,
                                           float(self.attn_temp), variant=self.warp_variant)
             plan = regs[s]
@@ -391,8 +412,9 @@ class MVS4net(nn.Module):
                 sel = ops.select_depth(hypo, self.depth_interals_ratio[s], self.inverse_depth, logits=plan(cor),
                                        want_logits=want_logits)
             if capture is not None:
-                capture[name] = {"cor_feats": cor.permute(0, 4, 1, 2, 3), "logits": sel["logits"],
-                                 "feats_cl": f}                                  # [N,B,h,w,C], view 0 = reference
+                capture[name] = {"cor_feats": cor.permute(0, 4, 1, 2, 3), "logits": sel["logits"]}
+                if views is None:
+                    capture[name]["feats_cl"] = f                                # [N,B,h,w,C], view 0 = reference
             # (x1 at the last stage is the identity, exactly: src = dst, lambda = 0.  The three coarse-stage launches stay on the
             #  main stream: on a stream of their own -- nothing in the cascade reads them -- the captured forward got SLOWER,
             #  1.174 against 1.129 ms alone and 850 against 1 108 depth-maps/s with two in flight, same box, alternating runs
@@ -407,7 +429,7 @@ class MVS4net(nn.Module):
             if self.inverse_depth:
                 st["inverse_min_depth"] = sel["inverse_min_depth"]
                 st["inverse_max_depth"] = sel["inverse_max_depth"]
-            if self.mono:
+            if self.mono and views is None:
                 st["mono_feat"] = ref_cl.permute(0, 3, 1, 2)                     # [B,C,h,w] view, channels-last memory
             prev = st
             outputs[name] = st

@@ -71,6 +71,22 @@ def pack_images(imgs):
     return out
 
 
+def pack_images_u8(imgs_u8):
+    """uint8 [V,H,W,3] (what an image file decodes to) -> [V,1,H,W,4] channels-last RGB0 float32, ``u8 / 255`` with a true
+    division: bit for bit ``pack_images`` of ``formats.read_img``'s floats, for all images of a scan in one launch."""
+    if not torch.is_tensor(imgs_u8) or not imgs_u8.is_cuda:
+        raise RuntimeError("mvster_amd.ops.pack_images_u8: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[3] != 3:
+        raise RuntimeError("pack_images_u8: expects uint8 [V,H,W,3], got %s %s" % (imgs_u8.dtype, tuple(imgs_u8.shape)))
+    x = imgs_u8.contiguous()
+    V, H, W, _ = x.shape
+    if V < 1 or H < 1 or W < 1 or x.data_ptr() % 4:
+        raise RuntimeError("pack_images_u8: empty or misaligned image stack %s" % (tuple(x.shape),))
+    out = torch.empty(V, 1, H, W, 4, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().mvster_pack_images_u8(_ptr(x), _ptr(out), V, H, W, _stream()), "pack_images_u8")
+    return out
+
+
 def forward_prologue(imgs, proj_list, depth_values, D, h, w, inverse):
     """``pack_images`` + ``relative_projection_multi`` + ``init_range`` (the first stage's hypotheses [B,D,h,w]) in one
     launch -> (packed, rt, hypo); the same bits as the three calls."""
@@ -133,6 +149,60 @@ def warp_agg_fwd_cl(ref_cl, src_cl, rt, hypo, G, group_cor=True, attn_fuse_d=Tru
                                          C, G, D, h, w, Hs, Ws, h * w * C, B * Hs * Ws * C, Hs * Ws * C,
                                          int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant), _stream())
     _lib.check(rc, "warp_agg_fwd")
+    return (out, wsum) if want_wsum else out
+
+
+def check_view_table(views, V, what="warp_agg_fwd_indexed"):
+    """A HOST view table (rows of 1 + NV view numbers, anything ``numpy.asarray`` takes) -> contiguous int32 array, after
+    checking ``0 <= index < V``: the kernels read the table from device memory and trust it."""
+    import numpy as np
+    t = np.ascontiguousarray(np.asarray(views, dtype=np.int64))
+    if t.ndim != 2 or t.shape[1] < 2:
+        raise RuntimeError("%s: the view table must be [B, 1 + NV] with NV >= 1, got %s" % (what, t.shape))
+    bad = np.argwhere((t < 0) | (t >= V))
+    if len(bad):
+        r, c = bad[0]
+        raise RuntimeError("%s: view index %d (row %d, column %d) lies outside the store of %d views" % (what, t[r, c], r, c, V))
+    return t.astype(np.int32)
+
+
+def warp_agg_fwd_indexed_cl(store, views, rt, hypo, G, group_cor=True, attn_fuse_d=True, attn_temp=2.0, want_wsum=False,
+                            variant=0):
+    """``warp_agg_fwd_cl`` reading its maps from a level store: store [V,h,w,C] (one pyramid level of every view of a
+    scan), views [B,1+NV] (column 0 = the reference view, the rest its sources; repeats allowed), rt [B,NV,12], hypo
+    [B,D,h,w] -> cor_feats [B,D,h,w,G] (and wsum), the bits of ``warp_agg_fwd_cl(store[views[:,0]], store[views[:,1:]].T...)``.
+    ``views`` on the host (array / list / CPU tensor) is range-checked and uploaded here; an int32 tensor already on the GPU is
+    used as it is -- the caller vouches for it (``check_view_table``), the kernel does not look."""
+    for t, n in ((store, "store"), (rt, "rt"), (hypo, "hypo")):
+        _chk(t, "warp_agg_fwd_indexed:" + n)
+    if store.dim() != 4:
+        raise RuntimeError("warp_agg_fwd_indexed: store must be [V,h,w,C], got %s" % (tuple(store.shape),))
+    V, h, w, C = store.shape
+    if torch.is_tensor(views) and views.is_cuda:
+        if views.dtype != torch.int32 or not views.is_contiguous() or views.device != store.device:
+            raise RuntimeError("warp_agg_fwd_indexed: a device view table must be contiguous int32 on the store's device")
+    else:
+        views = torch.from_numpy(check_view_table(views.numpy() if torch.is_tensor(views) else views, V)).to(store.device)
+    if views.dim() != 2 or views.shape[1] < 2:
+        raise RuntimeError("warp_agg_fwd_indexed: the view table must be [B, 1 + NV], got %s" % (tuple(views.shape),))
+    B, NV = views.shape[0], views.shape[1] - 1
+    D = hypo.shape[1]
+    if tuple(hypo.shape) != (B, D, h, w) or tuple(rt.shape) != (B, NV, 12):
+        raise RuntimeError("warp_agg_fwd_indexed: inconsistent shapes")
+    out = torch.empty(B, D, h, w, G, device=store.device, dtype=torch.float32)
+    wsum = torch.empty(B, D, h, w, device=store.device, dtype=torch.float32) if want_wsum else None
+    rc = _lib.load().mvster_warp_agg_fwd_indexed(_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), V, B, NV,
+                                                 C, G, D, h, w, int(group_cor), int(attn_fuse_d), float(attn_temp),
+                                                 int(variant), _stream())
+    if rc == _lib.ERR_UNSUPPORTED:
+        # a kernel form that is not instantiated indexed (csrc/warp_agg.hip, kIndexedOneThread / kIndexedLanes), or no kernel
+        # at all: one gather launch into the view-major batch, then the plain entry -- which raises in the second case
+        N = NV + 1
+        maps = torch.empty(N, B, h, w, C, device=store.device, dtype=torch.float32)
+        _lib.check(_lib.load().mvster_gather_views(_ptr(store), _ptr(views), _ptr(maps), V, B, N, h * w * C, _stream()),
+                   "gather_views")
+        return warp_agg_fwd_cl(maps[0], maps[1:], rt, hypo, G, group_cor, attn_fuse_d, attn_temp, want_wsum, variant)
+    _lib.check(rc, "warp_agg_fwd_indexed")
     return (out, wsum) if want_wsum else out
 
 

@@ -1,0 +1,483 @@
+"""Scan-level inference: images and cameras of a whole scan in, the depth and confidence maps of all its reference
+views out, on the GPU -- the reference's per-sample loop ``save_scene_depth`` (test_mvs4.py:170-268) as one call.
+
+What the loop recomputes and this path does not:
+
+* **FPN once per image.**  A scan of V images with R reference views of ``nviews`` views each runs FPN4 on ``R * nviews``
+  images in the loop; only V are distinct, and FPN4 in eval mode is a per-image function.  Here the FPN plan runs over the
+  distinct images in chunks of ``nviews`` (the per-sample batch, so ``conv_plan`` picks the same kernels) and writes the
+  four pyramid levels into per-scan *level stores* ``[V,h,w,C]``.
+* **One upload per image**, as 8-bit pixels (``ops.pack_images_u8``: 3 instead of 12 bytes per pixel).
+* **Cascade per reference view from the stores.**  ``MVS4net._cascade_eval`` -- the very body of the per-sample forward
+  after the FPN -- reads the stores through ``ops.warp_agg_fwd_indexed_cl`` and a device view table.  It is captured once
+  per scan shape as a hipGraph whose only per-sample inputs are ONE small device buffer (view table, projection stacks,
+  ``depth_values``: ~3.5 kB); ``in_flight`` instances replay on streams of their own.  The graph is a single chain of
+  launches; nothing here sets anything about hardware queues.
+* The maps stay on the device: ``reconstruct_scan`` hands them to ``fusion.fuse_scene`` where they are.
+
+Same kernels on the same operands as ``model(imgs, proj_matrices, depth_values)`` per sample: ``depth`` and
+``photometric_confidence`` are bit-equal to it (tests/test_gpu_scan.py).  Image resampling stays outside the path
+(DESIGN.md section 7): all images of a scan must have one admissible size.
+"""
+import collections
+import os
+import weakref
+
+import numpy as np
+import torch
+
+from . import formats, ops
+
+ScanPlan = collections.namedtuple("ScanPlan", "ref_views view_table proj depth_values fusion_pairs")
+ScanPlan.__doc__ = """Host planning of a scan (pure NumPy).  ``ref_views`` [R] view numbers that get a depth map, ``view_table``
+int32 [R,nviews] (column 0 = the reference view, then its sources cut / padded as ``formats.eval_view_list`` does),
+``proj`` dict stage1..4 -> [V,2,4,4] (``formats.stage_proj_matrices`` over ALL views: a sample's stack is
+``proj[stage][view_table[r]]``), ``depth_values`` [R,ndv], ``fusion_pairs`` the pairs with sources, full source lists."""
+
+
+def _as_pairs(pairs, V):
+    out = []
+    for entry in pairs:
+        r, srcs = int(entry[0]), [int(v) for v in entry[1]]
+        for v in [r] + srcs:
+            if not 0 <= v < V:
+                raise RuntimeError("infer_scan: pairs name view %d, which lies outside the scan's %d views" % (v, V))
+        out.append((r, srcs))
+    return out
+
+
+def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192):
+    """Per-view quarter-resolution intrinsics ``Ks`` [V,3,3] and extrinsics ``Es`` [V,4,4] (``formats.read_cam_file``),
+    ``depth_ranges`` [V] of (depth_min, depth_interval) or ready ``depth_values`` [V,ndv], ``pairs`` as
+    ``formats.read_pair_file`` -> ScanPlan.  View list per reference view as ``formats.eval_view_list`` +
+    ``formats.load_eval_sample``: sources cut to ``nviews - 1``, short lists padded by repeating the first source,
+    reference views without sources dropped."""
+    Ks = np.asarray(Ks, dtype=np.float32)
+    Es = np.asarray(Es, dtype=np.float32)
+    V = len(Ks)
+    if Ks.shape != (V, 3, 3) or Es.shape != (V, 4, 4):
+        raise RuntimeError("infer_scan: Ks must be [V,3,3] and Es [V,4,4], got %s and %s" % (Ks.shape, Es.shape))
+    if nviews < 2:
+        raise RuntimeError("infer_scan: nviews = %d (at least one source view is needed)" % nviews)
+    pairs = _as_pairs(pairs, V)
+    dr = np.asarray(depth_ranges, dtype=np.float32)
+    if dr.ndim != 2 or dr.shape[0] != V or dr.shape[1] < 2:
+        raise RuntimeError("infer_scan: depth_ranges must be [V,2] (depth_min, depth_interval) or depth_values [V,ndv], "
+                           "got %s for %d views" % (dr.shape, V))
+    ref_views, table, dvs, fusion_pairs = [], [], [], []
+    for r, srcs in pairs:
+        if not srcs:
+            continue                                                        # (read_pair_file drops these too)
+        fusion_pairs.append((r, list(srcs)))
+        if len(srcs) < nviews:
+            srcs = srcs + [srcs[0]] * (nviews - len(srcs))                  # general_eval4.py:47-49
+        ref_views.append(r)
+        table.append([r] + srcs[:nviews - 1])
+        if dr.shape[1] == 2:
+            # (the Python floats read_cam_file returns; a float32 array holds them exactly when they came from one)
+            dvs.append(formats.depth_value_range(float(depth_ranges[r][0]), float(depth_ranges[r][1]), ndepths))
+        else:
+            dvs.append(dr[r])
+    if not ref_views:
+        raise RuntimeError("infer_scan: no reference view with a source view in pairs")
+    return ScanPlan(np.array(ref_views, dtype=np.int64), np.array(table, dtype=np.int32),
+                    formats.stage_proj_matrices(Ks, Es), np.stack(dvs).astype(np.float32), fusion_pairs)
+
+
+def store_bytes(V, H, W, base_channels=8):
+    """Bytes of the four level stores: ``V * H * W * 15 * 4`` for the shipped FPN (8 + 16/4 + 32/16 + 64/64 channels per
+    full-resolution pixel)."""
+    c = base_channels
+    return V * (H * W * c + (H // 2) * (W // 2) * 2 * c + (H // 4) * (W // 4) * 4 * c + (H // 8) * (W // 8) * 8 * c) * 4
+
+
+def _check_images(images):
+    """-> ("u8", [V,H,W,3]) or ("f32", [V,3,H,W]) as given (array or tensor, not copied), after the shape checks."""
+    if not torch.is_tensor(images) and not isinstance(images, np.ndarray):
+        images = list(images)
+        if not images:
+            raise RuntimeError("infer_scan: no images")
+        first = tuple(images[0].shape)
+        for i, im in enumerate(images):
+            if tuple(im.shape) != first:
+                raise RuntimeError("infer_scan: image %d is %s but image 0 is %s: all views of a scan must have one size "
+                                   "(resize the images first)" % (i, tuple(im.shape), first))
+        images = torch.stack(images) if torch.is_tensor(images[0]) else np.stack(images)
+    dt = images.dtype
+    if dt in (torch.uint8, np.dtype(np.uint8)):
+        kind = "u8"
+        if images.ndim != 4 or images.shape[3] != 3:
+            raise RuntimeError("infer_scan: uint8 images must be [V,H,W,3], got %s" % (tuple(images.shape),))
+        H, W = images.shape[1], images.shape[2]
+    elif dt in (torch.float32, np.dtype(np.float32)):
+        kind = "f32"
+        if images.ndim != 4 or images.shape[1] != 3:
+            raise RuntimeError("infer_scan: float32 images must be [V,3,H,W], got %s" % (tuple(images.shape),))
+        H, W = images.shape[2], images.shape[3]
+    else:
+        raise RuntimeError("infer_scan: images must be uint8 [V,H,W,3] or float32 [V,3,H,W], got %s" % (dt,))
+    if H % 64 or W % 64 or H == 0 or W == 0:
+        raise RuntimeError("infer_scan: image size %dx%d: H and W must be multiples of 64 (resampling stays outside the "
+                           "path: resize the images first)" % (H, W))
+    return kind, images, int(images.shape[0]), int(H), int(W)
+
+
+class ScanResult(dict):
+    """What ``infer_scan`` returns: ``ref_views`` [R] (view numbers, host), ``depth`` and ``photometric_confidence`` [R,H,W]
+    on the GPU, ``Ks`` [V,3,3] / ``Es`` [V,4,4] at output resolution (the stage-4 camera ``write_cam`` gets in the
+    reference), ``pairs`` (reference views with sources, full source lists: what fusion reads), ``view_ids`` (file
+    numbers of the views), ``stats`` (``fpn_runs``, ``replays``, ``captured``) and whatever else ``keep`` named."""
+
+    def timings(self):
+        """Milliseconds per phase (HIP events recorded by ``infer_scan``; synchronises)."""
+        torch.cuda.synchronize()
+        ev = self.get("events", {})
+        return {k: a.elapsed_time(b) for k, (a, b) in ev.items()}
+
+
+class _Instance:
+    """One captured cascade: a static per-sample input buffer, the graph, its static outputs, a stream.  Holds no reference
+    back to its runner: a dropped runner must free its graphs by reference count, at once -- a hipGraph destroyed later by
+    the cycle collector, while this thread captures another one, aborts the process."""
+
+    def __init__(self, runner, regs):
+        dev = runner.dev
+        self.stream = torch.cuda.Stream(device=dev)
+        self.buf = torch.zeros(runner.row, dtype=torch.float32, device=dev)
+        n = runner.nviews
+        self.views = self.buf[:n].view(torch.int32).view(1, n)
+        self.pms = [self.buf[o:o + n * 32].view(1, n, 2, 4, 4) for o in runner.proj_off]
+        self.dv = self.buf[runner.dv_off:runner.dv_off + runner.ndv].view(1, runner.ndv)
+        self.graph = None
+        self.outputs = None
+        self.regs, self.stores, self.shape = regs, runner.stores, (n, runner.H, runner.W)
+
+    def run(self, model):
+        n, H, W = self.shape
+        rts = ops.relative_projection_multi(self.pms)
+        depth_interval = None
+        if not model.inverse_depth:
+            depth_interval = (self.dv[:, -1] - self.dv[:, 0]) / self.dv.size(1)
+        return model._cascade_eval(self.stores, self.regs, n, 1, H, W, rts, self.dv, depth_interval, views=self.views)
+
+    def capture(self, model):
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            self.outputs = self.run(model)
+
+
+class _ScanRunner:
+    """Level stores + captured cascades of one (model state, V, H, W, nviews, ndv) combination; the captured instances
+    grow with the largest ``in_flight`` asked for."""
+
+    def __init__(self, model, V, H, W, nviews, ndv, stamp):
+        self.dev = next(model.parameters()).device
+        self.V, self.H, self.W, self.nviews, self.ndv, self.stamp = V, H, W, nviews, ndv, stamp
+        c = model.feature.out_channels                                       # [8c, 4c, 2c, c] for stages 1..4
+        self.stores = [torch.empty(V, H >> (3 - s), W >> (3 - s), c[s], device=self.dev, dtype=torch.float32)
+                       if s < model.num_stage else None for s in range(4)]
+        # per-sample row: view table (int32 bits), one projection stack per stage, depth_values; 64-float segments
+        seg = lambda k: (k + 63) // 64 * 64
+        off = seg(nviews)
+        self.proj_off = []
+        for _ in range(model.num_stage):
+            self.proj_off.append(off)
+            off += seg(nviews * 32)
+        self.dv_off = off
+        self.row = off + seg(ndv)
+        self.plans = model._get_plans()                                      # (kept alive: the graphs hold pointers into them)
+        self.instances = []
+
+    def rows(self, plan, num_stage):
+        """All per-sample rows of a scan on the host: [R, row] float32 (the view numbers as raw int32 bits)."""
+        R = len(plan.ref_views)
+        host = np.zeros((R, self.row), dtype=np.float32)
+        host[:, :self.nviews] = plan.view_table.view(np.float32)
+        for s in range(num_stage):
+            pm = plan.proj["stage%d" % (s + 1)][plan.view_table]            # [R,nviews,2,4,4]
+            host[:, self.proj_off[s]:self.proj_off[s] + self.nviews * 32] = pm.reshape(R, -1)
+        host[:, self.dv_off:self.dv_off + self.ndv] = plan.depth_values
+        return host
+
+
+_RUNNERS = weakref.WeakKeyDictionary()          # model -> _ScanRunner (one scan shape resident per model: the stores are large)
+
+
+def _runner(model, V, H, W, nviews, ndv):
+    stamp = model._state_stamp()
+    from .graph import ForwardCache
+    # (the switches that pick kernels or launches: flipped between two calls they are a different graph)
+    cfg = ForwardCache.key(model, [torch.empty(1, 3, 1, 1)], {}, torch.empty(1, ndv))[-1]
+    key = (V, H, W, nviews, ndv, stamp, cfg)
+    hit = _RUNNERS.get(model)
+    if hit is None or hit[0] != key:
+        if hit is not None:
+            hit[1].instances.clear()             # the old graphs and stores go now, before anything new is allocated or captured
+            hit = None
+            del _RUNNERS[model]
+        hit = _RUNNERS[model] = (key, _ScanRunner(model, V, H, W, nviews, ndv, stamp))
+    return hit[1]
+
+
+def _run_fpn(model, runner, kind, dev_images, chunk):
+    """The FPN plan over the distinct images, ``chunk`` at a time (last chunk padded by repeating its last image), each
+    level into its store.  -> number of plan runs."""
+    fpn = runner.plans[0]
+    V = runner.V
+    packed = ops.pack_images_u8(dev_images) if kind == "u8" else None        # [V,1,H,W,4], one launch for the scan
+    runs = 0
+    for a in range(0, V, chunk):
+        b = min(V, a + chunk)
+        idx = list(range(a, b)) + [b - 1] * (chunk - (b - a))
+        if kind == "u8":
+            x = packed[a:b] if b - a == chunk else packed[idx]
+        else:
+            x = ops.pack_images([dev_images[i:i + 1] for i in idx])
+        c0, c1, c3, f1 = fpn.trunk(x)
+        levels = list(fpn.coarse(c3, f1)) + (list(fpn.tail(c0, c1, f1)) if model.num_stage > 2 else [None, None])
+        for s in range(model.num_stage):
+            runner.stores[s][a:b].copy_(levels[s][:b - a, 0])
+        runs += 1
+    return runs
+
+
+@torch.no_grad()
+def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2,
+               keep=("depth", "photometric_confidence"), ndepths=192, fpn_chunk=None, max_store_bytes=None, view_ids=None):
+    """Depth and confidence maps of all reference views of a scan.
+
+    ``images``: uint8 [V,H,W,3] (NumPy, or a tensor on the GPU) or float32 [V,3,H,W] in 0..1, or a sequence of per-view
+    arrays; ``Ks`` [V,3,3] / ``Es`` [V,4,4]: per-view intrinsics in the quarter-resolution convention of
+    ``formats.read_cam_file`` / ``formats.stage_proj_matrices`` and extrinsics; ``depth_ranges`` [V,2] = (depth_min,
+    depth_interval) per view as ``read_cam_file`` returns them, or ready ``depth_values`` [V,ndv]; ``pairs`` as
+    ``formats.read_pair_file``, indexing the V views.  All views must have one admissible size (H, W multiples of 64);
+    anything else raises, as ``formats.load_eval_sample`` does.
+
+    ``in_flight`` captured cascades replay on streams of their own.  ``keep``: the entries of the forward's output dict
+    to return as [R,...] stacks -- last-stage names (``"depth"``) or ``"stage2.depth"``; after each replay only these
+    are copied out of the graph's static outputs.  ``fpn_chunk``: images per FPN run (default ``nviews``: the
+    per-sample batch, the only value that carries the bit-equality with the per-sample forward).  ``max_store_bytes``:
+    raise if the level stores (``store_bytes``) would exceed it.  -> ScanResult."""
+    kind, images, V, H, W = _check_images(images)
+    if len(Ks) != V or len(Es) != V:
+        raise RuntimeError("infer_scan: %d images for %d intrinsics and %d extrinsics" % (V, len(Ks), len(Es)))
+    plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths)
+    if in_flight < 1:
+        raise RuntimeError("infer_scan: in_flight = %d" % in_flight)
+    chunk = int(fpn_chunk or nviews)
+    if not 1 <= chunk <= 16:
+        raise RuntimeError("infer_scan: fpn_chunk = %d (1..16 images per FPN run)" % chunk)
+    need = store_bytes(V, H, W, model.feature.out_channels[-1])
+    if max_store_bytes is not None and need > max_store_bytes:
+        raise RuntimeError("infer_scan: the level stores of %d views of %dx%d need %d bytes (%.2f GB), more than "
+                           "max_store_bytes = %d" % (V, H, W, need, need / 1e9, max_store_bytes))
+    if model.training:
+        raise RuntimeError("infer_scan runs the eval forward: call model.eval() first")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("mvster_amd.scan.infer_scan runs on MI355X only: move the model to the GPU (there is no CPU "
+                           "fallback)")
+    keep = tuple(keep)
+    R = len(plan.ref_views)
+    ops.check_view_table(plan.view_table, V, "infer_scan")                  # (the kernels trust the device table)
+    main = torch.cuda.current_stream(dev)
+    ev = {k: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for k in ("upload", "fpn", "cascade")}
+
+    with torch.cuda.device(dev):
+        ev["upload"][0].record(main)
+        if torch.is_tensor(images):
+            dev_images = images.to(dev).contiguous()
+        else:
+            dev_images = torch.from_numpy(np.ascontiguousarray(images)).to(dev)
+        runner = _runner(model, V, H, W, nviews, plan.depth_values.shape[1])
+        samples = torch.from_numpy(runner.rows(plan, model.num_stage)).to(dev)   # all per-sample inputs: ONE upload
+        ev["upload"][1].record(main)
+
+        ev["fpn"][0].record(main)
+        fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk)
+        ev["fpn"][1].record(main)
+
+        # [K,R,...] stacks of the kept maps; same-shaped ones share one allocation (one staging copy moves them all)
+        captured_now = len(runner.instances) < in_flight
+        while len(runner.instances) < in_flight:
+            inst = _Instance(runner, runner.plans[1])
+            inst.buf.copy_(samples[0])
+            if not runner.instances:                                         # eager once (plans, allocator), then capture
+                first = inst.run(model)
+                for name in keep:
+                    _pick(first, name)                                       # (a wrong name raises before the capture)
+                del first
+            torch.cuda.synchronize(dev)
+            inst.capture(model)
+            runner.instances.append(inst)
+        insts = runner.instances[:in_flight]
+        srcs = [[_pick(inst.outputs, name) for name in keep] for inst in insts]
+        shapes = [tuple(t.shape[1:]) for t in srcs[0]]
+        same = len(set(shapes)) == 1
+        if same:
+            maps = torch.empty((len(keep), R) + shapes[0], device=dev, dtype=torch.float32)
+            stacks = [maps[k] for k in range(len(keep))]
+        else:
+            maps = None
+            stacks = [torch.empty((R,) + sh, device=dev, dtype=torch.float32) for sh in shapes]
+
+        ev["cascade"][0].record(main)
+        for inst in insts:
+            inst.stream.wait_stream(main)
+        for r in range(R):
+            i = r % in_flight
+            inst = insts[i]
+            with torch.cuda.stream(inst.stream):
+                inst.buf.copy_(samples[r], non_blocking=True)                # view table + projections + depth range
+                inst.graph.replay()
+                torch._foreach_copy_([st[r:r + 1] for st in stacks], srcs[i])   # only the kept maps leave the graph's buffers
+        for inst in insts:
+            main.wait_stream(inst.stream)
+        ev["cascade"][1].record(main)
+
+    k4 = plan.proj["stage4"] if "stage4" in plan.proj else None
+    res = ScanResult(ref_views=plan.ref_views, pairs=plan.fusion_pairs,
+                     Ks=k4[:, 1, :3, :3].copy(), Es=k4[:, 0].copy(),
+                     view_ids=list(range(V)) if view_ids is None else [int(v) for v in view_ids],
+                     stats={"fpn_runs": fpn_runs, "replays": R, "captured": captured_now, "store_bytes": need}, events=ev)
+    for name, st in zip(keep, stacks):
+        res[name] = st
+    res.maps, res.map_names = maps, keep
+    return res
+
+
+def _pick(outputs, name):
+    cur = outputs
+    for part in name.split("."):
+        if not isinstance(cur, dict) or part not in cur:
+            raise RuntimeError("infer_scan: keep names %r, which is not an entry of the forward's outputs" % name)
+        cur = cur[part]
+    if not torch.is_tensor(cur):
+        raise RuntimeError("infer_scan: keep names %r, which is not a tensor" % name)
+    return cur
+
+
+def read_scan_folder(datapath, scan, interval_scale=1.06, ndepths=192):
+    """``datapath/scan/{images_post|images}/%08d.jpg``, ``cams/%08d_cam.txt``, ``pair.txt`` -> dict with ``images`` (list of
+    uint8 [H,W,3]), ``Ks``, ``Es``, ``depth_ranges``, ``pairs`` (indices into the views) and ``view_ids`` (their file
+    numbers, sorted): everything ``infer_scan`` takes.  Every file is read once."""
+    from PIL import Image
+    root = os.path.join(datapath, scan)
+    file_pairs = formats.read_pair_file(os.path.join(root, "pair.txt"))
+    view_ids = sorted({v for r, srcs in file_pairs for v in [r] + srcs})
+    paths = {}
+    for v in view_ids:
+        img = os.path.join(root, "images_post", "{:0>8}.jpg".format(v))
+        if not os.path.exists(img):
+            img = os.path.join(root, "images", "{:0>8}.jpg".format(v))
+        cam = os.path.join(root, "cams", "{:0>8}_cam.txt".format(v))
+        for f in (img, cam):
+            if not os.path.exists(f):
+                raise RuntimeError("infer_scan_folder: pair.txt names view %d, but %s does not exist" % (v, f))
+        paths[v] = (img, cam)
+    slot = {v: i for i, v in enumerate(view_ids)}
+    images, Ks, Es, ranges = [], [], [], []
+    for v in view_ids:
+        images.append(np.array(Image.open(paths[v][0]), dtype=np.uint8))
+        K, E, dmin, dint = formats.read_cam_file(paths[v][1], interval_scale, ndepths)
+        Ks.append(K)
+        Es.append(E)
+        ranges.append((dmin, dint))
+    return dict(images=images, Ks=np.stack(Ks), Es=np.stack(Es), depth_ranges=ranges, view_ids=view_ids,
+                pairs=[(slot[r], [slot[v] for v in srcs]) for r, srcs in file_pairs])
+
+
+def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192):
+    """Host planning of ``infer_scan_folder`` -> (the ``read_scan_folder`` dict, ScanPlan); no device work."""
+    sc = read_scan_folder(datapath, scan, interval_scale, ndepths)
+    _check_images(sc["images"])
+    return sc, plan_scan(sc["Ks"], sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths)
+
+
+def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, **kw):
+    """``infer_scan`` on a scan folder in the reference's layout (``general_eval4.MVSDataset``).  The result's
+    ``ref_views`` / ``pairs`` index ``view_ids`` (the file numbers)."""
+    sc = read_scan_folder(datapath, scan, interval_scale, ndepths)
+    res = infer_scan(model, sc["images"], sc["Ks"], sc["Es"], sc["depth_ranges"], sc["pairs"], nviews=nviews,
+                     ndepths=ndepths, view_ids=sc["view_ids"], **kw)
+    res["images"] = sc["images"]
+    return res
+
+
+def _images_u8_hwc(images):
+    """The scan's images as uint8 [V,H,W,3] on the host (float 0..1 inputs: clip(x * 255) truncated, test_mvs4.py:262-264)."""
+    kind, images, _, _, _ = _check_images(images)
+    if torch.is_tensor(images):
+        images = images.detach().cpu().numpy()
+    if kind == "u8":
+        return images
+    return np.clip(np.transpose(images, (0, 2, 3, 1)) * 255, 0, 255).astype(np.uint8)
+
+
+def write_scan_outputs(result, images, out_folder):
+    """The reference's per-scan output layout (test_mvs4.py:213-264): ``depth_est/%08d.pfm``, ``confidence/%08d.pfm``,
+    ``cams/%08d_cam.txt`` (stage-4 camera), ``images/%08d.jpg`` for every reference view, numbered by
+    ``result['view_ids']`` -- what ``fusion.filter_depth(pair_folder, out_folder, out_folder, ply)`` reads.  The two map
+    stacks leave the device through ONE pinned staging copy."""
+    from PIL import Image
+    depth, conf = result["depth"], result["photometric_confidence"]
+    maps, names = getattr(result, "maps", None), getattr(result, "map_names", ())
+    if maps is not None and "depth" in names and "photometric_confidence" in names:
+        # (infer_scan keeps same-shaped stacks in one allocation: the whole of it in one copy)
+        stage = torch.empty(maps.shape, dtype=torch.float32).pin_memory()
+        stage.copy_(maps, non_blocking=True)
+        torch.cuda.current_stream(maps.device).synchronize()
+        depth_h, conf_h = stage[names.index("depth")].numpy(), stage[names.index("photometric_confidence")].numpy()
+    else:
+        stage = torch.empty((2,) + tuple(depth.shape), dtype=torch.float32).pin_memory()
+        torch._foreach_copy_([stage[0], stage[1]], [depth, conf])
+        torch.cuda.current_stream(depth.device).synchronize()
+        depth_h, conf_h = stage[0].numpy(), stage[1].numpy()
+    imgs = _images_u8_hwc(images)
+    for sub in ("depth_est", "confidence", "cams", "images"):
+        os.makedirs(os.path.join(out_folder, sub), exist_ok=True)
+    ids = result["view_ids"]
+    for i, r in enumerate(result["ref_views"]):
+        name = "{:0>8}".format(ids[int(r)])
+        formats.save_pfm(os.path.join(out_folder, "depth_est", name + ".pfm"), np.ascontiguousarray(depth_h[i]))
+        formats.save_pfm(os.path.join(out_folder, "confidence", name + ".pfm"), np.ascontiguousarray(conf_h[i]))
+        cam = np.zeros((2, 4, 4), dtype=np.float32)
+        cam[0] = result["Es"][int(r)]
+        cam[1, :3, :3] = result["Ks"][int(r)]
+        formats.write_cam(os.path.join(out_folder, "cams", name + "_cam.txt"), cam)
+        Image.fromarray(imgs[int(r)]).save(os.path.join(out_folder, "images", name + ".jpg"))
+
+
+def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres_view=5, plyfilename=None, **kw):
+    """``infer_scan`` followed by ``fusion.fuse_scene`` on the device tensors: the reference's ``save_scene_depth`` +
+    ``filter_depth`` (test_mvs4.py:170-268, :331-421) without leaving the GPU.  -> the ``fusion.SceneResult`` (with the
+    ``ScanResult`` as its ``scan`` attribute); writes the point cloud to ``plyfilename`` if given.
+
+    Every source view a reference view's pair lists must have a depth map of its own, i.e. be a reference view with
+    sources itself (the reference's ``filter_depth`` reads its ``depth_est`` file).  Colours come from the INPUT images,
+    not from the re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same,
+    colours differ by the JPEG re-encoding the reference adds."""
+    from . import fusion
+    kind, images, V, H, W = _check_images(images)
+    scan = infer_scan(model, images, Ks, Es, depth_ranges, pairs, **kw)
+    slot = {int(r): i for i, r in enumerate(scan["ref_views"])}
+    fpairs = []
+    for r, srcs in scan["pairs"]:
+        for v in srcs:
+            if v not in slot:
+                raise RuntimeError("reconstruct_scan: reference view %d lists source view %d, which has no depth map (it "
+                                   "is not a reference view with sources in pairs)" % (r, v))
+        fpairs.append((slot[r], [slot[v] for v in srcs]))
+    dev = scan["depth"].device
+    idx = torch.from_numpy(np.asarray(scan["ref_views"])).to(dev)
+    img = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
+    img = img.to(dev)[idx]
+    if kind == "f32":
+        img = img.permute(0, 2, 3, 1).contiguous()
+    refs = np.asarray(scan["ref_views"])
+    res = fusion.fuse_scene(scan["depth"], scan["photometric_confidence"], img, scan["Ks"][refs], scan["Es"][refs], fpairs,
+                            conf, thres_view, device=dev)
+    res.scan = scan
+    if plyfilename is not None:
+        fusion.write_ply(plyfilename, res.vertices())
+    return res
