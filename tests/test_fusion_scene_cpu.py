@@ -2,10 +2,8 @@
 any GPU call), ``scene_tables`` against ``view_matrices``, and the per-pixel arithmetic of mvster_amd/csrc/geo_math.h --
 the functions geo_filter.hip and geo_scene.hip inline -- compiled for the host and run serially over a scan against
 oracle/geo_filter_oracle.py."""
-import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +11,6 @@ import pytest
 from tests import fusion_scene_cases as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTMATH = os.path.join(ROOT, "tests", "hostmath")
 NEW = ("mvster_geo_scene_blocks", "mvster_geo_scene_filter", "mvster_geo_scene_emit")
 
 
@@ -27,14 +24,7 @@ def lib():
 
 @pytest.fixture(scope="module")
 def ghm():
-    so = os.path.join(HOSTMATH, "libgeohostmath.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", so,
-                           os.path.join(HOSTMATH, "geo_hostmath.cpp")])
-    h = ctypes.CDLL(so)
-    h.hm_geo_scene.restype = ctypes.c_long
-    h.hm_geo_scene.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_float,
-                                                                          ctypes.c_float] + [ctypes.c_void_p] * 9
-    return h
+    return C.load_geo_hostmath()
 
 
 def test_scene_entry_points_are_declared_exported_and_bound(lib):
@@ -114,42 +104,93 @@ def test_fuse_scene_refuses_cpu_only_inputs():
         fusion.fuse_scene(sc["depths"], sc["conf"], sc["images"], sc["Ks"], sc["Es"], sc["pairs"], 0.3, 2, device="cpu")
 
 
-def run_host_scene(ghm, sc, conf_thres=C.CONF_THRES, thres_view=C.THRES_VIEW):
-    from mvster_amd import fusion
-    t = fusion.scene_tables(sc["pairs"], sc["Ks"], sc["Es"])
-    R, smax = t.pair_table.shape
-    V, H, W = sc["depths"].shape
-    out = dict(geo_mask_sum=np.zeros((R, H, W), np.int32), depth_est_averaged=np.zeros((R, H, W), np.float64),
-               photo_mask=np.zeros((R, H, W), np.uint8), geo_mask=np.zeros((R, H, W), np.uint8),
-               final_mask=np.zeros((R, H, W), np.uint8), view_mask=np.zeros((R, smax, H, W), np.uint8),
-               points=np.zeros((R * H * W, 3), np.float32), colors=np.zeros((R * H * W, 3), np.uint8),
-               counts=np.zeros(R, np.int64))
-    ins = [np.ascontiguousarray(a) for a in (sc["depths"], sc["conf"], sc["images"], t.pair_table, t.ref_view, t.ref_mats,
-                                             t.view_mats)]
-    assert ins[0].dtype == ins[1].dtype == ins[2].dtype == np.float32
-    m = ghm.hm_geo_scene(*[a.ctypes.data for a in ins], R, smax, V, H, W, conf_thres, thres_view, 1.0, 0.01,
-                         *[out[k].ctypes.data for k in ("geo_mask_sum", "depth_est_averaged", "photo_mask", "geo_mask",
-                                                        "final_mask", "view_mask", "points", "colors", "counts")])
-    assert m >= 0
-    for k in ("photo_mask", "geo_mask", "final_mask"):
-        out[k] = out[k].astype(bool)
-    out["points"], out["colors"] = out["points"][:m], out["colors"][:m]
-    return out
+run_host_scene = C.run_host_scene
+
+# small_scene with its floor of 0.3, then every hard scene at the thres_view values HARD_CASES lists, with half of the
+# oracle-only kept fraction written there as the floor
+SCENE_CASES = [pytest.param(None, C.THRES_VIEW, 0.3, id="small_scene")] + [
+    pytest.param(case, tv, kept / 2, id="%s-tv%d" % (C.hard_id(case), tv)) for case in C.HARD_CASES
+    for tv, kept in sorted(case[4].items())]
 
 
-def test_geo_math_host_scene_vs_oracle(ghm):
+@pytest.mark.parametrize("case,thres_view,floor", SCENE_CASES)
+def test_geo_math_host_scene_vs_oracle(ghm, case, thres_view, floor):
     """The shared header, serially over the scan: votes, average, back-projection and emission order against the oracle.
     Bounds: vote flips on at most 2e-4 of the pixel-views, depth_est_averaged within 1e-6 relative where the votes
-    agree, world points within one float32 ulp of the cloud's largest coordinate where the final masks agree, colours
-    equal."""
-    sc = C.small_scene()
-    want_views, want_vertices = C.oracle_scene(sc)
-    got = run_host_scene(ghm, sc)
-    fig = C.compare_with_oracle(got, want_views, want_vertices, view_masks=got["view_mask"])
+    agree (NaN, +-inf and zero exactly where the oracle has them), world points within one float32 ulp of the cloud's
+    largest coordinate where the final masks agree, colours equal."""
+    sc = C.small_scene() if case is None else C.hard_scene(*case[:4])
+    want_views, want_vertices = C.oracle_scene(sc, thres_view=thres_view)
+    if case is not None:                             # the floor in HARD_CASES is what the oracle alone keeps here
+        kept = float(np.stack([w["final_mask"] for w in want_views]).mean())
+        assert abs(kept - case[4][thres_view]) < 5e-5 and kept > 0, (kept, case[4])
+    got = run_host_scene(ghm, sc, thres_view=thres_view)
+    fig = C.compare_with_oracle(got, want_views, want_vertices, view_masks=got["view_mask"], floor=floor,
+                                thres_view=thres_view)
     print("geo_math host scene vs oracle:", fig)
     if fig["final_mask_mismatch_pixels"] == 0:                               # then the clouds line up vertex by vertex
         assert len(got["points"]) == len(want_vertices)
         assert np.array_equal(got["colors"][:, 0], want_vertices["red"])
+
+
+def test_hard_cases_cover_the_sizes_the_kernels_go_wrong_at():
+    """The list itself: every kind, a map below one wave, between a wave and a workgroup, 256k + 1, 256k - 1, an odd
+    width with an even height, a wide and a tall thin shape -- and the degenerate kinds really hold every bad value."""
+    hw = [c[0] * c[1] for c in C.HARD_CASES]
+    assert {c[3] for c in C.HARD_CASES} == set(C.HARD_KINDS)
+    assert any(n < 64 for n in hw) and any(64 < n < 256 for n in hw)
+    assert any(n > 256 and n % 256 == 1 for n in hw) and any(n > 256 and n % 256 == 255 for n in hw)
+    assert any(c[1] % 2 == 1 and c[0] % 2 == 0 for c in C.HARD_CASES)
+    assert any(c[0] >= 100 * c[1] for c in C.HARD_CASES) and any(c[1] >= 100 * c[0] for c in C.HARD_CASES)
+    d = C.hard_scene(61, 83, 5, "degenerate")["depths"]
+    assert np.isnan(d).any() and np.isposinf(d).any() and (d == 0).any() and (d < 0).any()
+    assert (d == np.float32(1e-30)).any() and (d == np.float32(1e30)).any()
+    a, b = C.hard_scene(37, 53, 6, "perK"), C.hard_scene(37, 53, 6, "perK")
+    assert a["depths"].tobytes() == b["depths"].tobytes() and a["Ks"].tobytes() == b["Ks"].tobytes()    # deterministic
+    assert len({k.tobytes() for k in a["Ks"]}) == 6 and max(len(s) for _, s in a["pairs"]) > min(len(s) for _, s in a["pairs"])
+
+
+def test_compare_with_oracle_understands_non_finite_values():
+    """assert_same_values: NaN matches NaN only, inf matches inf of the same sign only, zero stays zero."""
+    want = np.array([1.0, np.nan, np.inf, -np.inf, 0.0, 2.0])
+    assert C.assert_same_values(want.copy(), want, C.AVG_REL) == 0.0
+    assert C.assert_same_values(want * np.where(np.isfinite(want), 1 + 5e-7, 1), want, C.AVG_REL) > 0
+    for k, bad in [(0, np.nan), (1, 1.0), (2, -np.inf), (3, np.inf), (2, 1e308), (4, 1e-300), (5, 2.0 + 1e-5), (0, 0.0)]:
+        got = want.copy()
+        got[k] = bad
+        with pytest.raises(AssertionError):
+            C.assert_same_values(got, want, C.AVG_REL)
+
+
+@pytest.mark.parametrize("H,W", [(61, 83), (96, 128), (9, 13), (35, 256)])
+def test_pattern_scene_every_pixel_gets_every_vote(ghm, H, W):
+    """The premise of the compaction tests on the GPU: with one camera and one noise-free depth map for all views the
+    oracle casts every vote, so final_mask is the confidence pattern; the host build agrees and emits the predicted
+    colours in the predicted order."""
+    V = 3
+    pattern = C.pattern_mask("random", V, H, W)
+    sc = C.pattern_scene(H, W, V, pattern)
+    f32 = dict(sc, images=sc["images"].astype(np.float32) / np.float32(255.0))
+    want_views, _ = C.oracle_scene(f32, conf_thres=C.PATTERN_CONF_THRES, thres_view=1)
+    for w in want_views:
+        assert (w["geo_mask_sum"] == V - 1).all()
+    final, counts, colors = C.expected_pattern_cloud(sc, pattern)
+    assert np.array_equal(np.stack([w["final_mask"] for w in want_views]), final)
+    got = run_host_scene(ghm, sc, conf_thres=C.PATTERN_CONF_THRES, thres_view=1)
+    assert (got["geo_mask_sum"] == V - 1).all() and np.array_equal(got["final_mask"], final)
+    assert np.array_equal(got["counts"], counts) and np.array_equal(got["colors"], colors)
+
+
+def test_pattern_masks_are_what_their_names_say():
+    R, H, W = 3, 61, 83
+    hw = H * W
+    m = {n: C.pattern_mask(n, R, H, W).reshape(R, hw) for n in C.PATTERNS}
+    assert m["ones"].all() and not m["zeros"].any()
+    assert m["first"].sum() == R and m["first"][:, 0].all() and m["last"].sum() == R and m["last"][:, hw - 1].all()
+    assert m["lane63"].sum() == R * (hw // 64) and m["lane63"][:, 63::64].all()
+    assert m["every65"][:, ::65].all() and m["every65"].sum() == R * len(range(0, hw, 65))
+    assert 0.45 < m["random"].mean() < 0.55
+    assert not m["per_view"][0].any() and m["per_view"][R - 1].all() and 0.4 < m["per_view"][1].mean() < 0.6
 
 
 def test_geo_math_host_scene_thres_view_above_every_source_count(ghm):
