@@ -43,6 +43,18 @@ int mvster_pack_images(const float* const* imgs, int N, float* out, int B, int H
  * one launch and from a quarter of the bytes. */
 int mvster_pack_images_u8(const unsigned char* imgs, float* out, int V, int H, int W, void* stream);
 
+/* mvster_pack_images_u8 with the evaluation loader's input scaling in the same pass (datasets/general_eval4.py:92-109:
+ * cv2.resize with default arguments -- bilinear, on read_img's floats): imgs uint8 [V,Hs,Ws,3] (4-byte aligned) ->
+ * out [V,1,Hd,Wd,4] float RGB0 and, where out_u8 is not NULL, out_u8 [V,Hd,Wd,3] = trunc(clip(x * 255, 0, 255)), the pixels
+ * test_mvs4.py:262-264 writes to images/.  tables: 2 Wd + 2 Hd 32-bit words (16-byte aligned) -- first tap sx [Wd] (int32),
+ * fraction fx [Wd] (float32), then sy [Hd], fy [Hd] -- built on the host as OpenCV builds xofs / alpha
+ * (mvster_amd.formats.resize_tables); arithmetic in csrc/resize_math.h.  At Ws == 2 Wd and Hs == 2 Hd the 2 x 2 mean of
+ * OpenCV's area path.  Hs == Hd and Ws == Wd gives the bits of mvster_pack_images_u8.  The loader never enlarges:
+ * Hd > Hs or Wd > Ws, like Hd / Wd that are not positive multiples of 64, is MVSTER_ERR_SHAPE.  The tables are trusted
+ * for the values, not for the addresses: tap indices are clamped into the image. */
+int mvster_resize_pack_images_u8(const unsigned char* imgs, const void* tables, float* out, unsigned char* out_u8, int V, int Hs,
+                                 int Ws, int Hd, int Wd, void* stream);
+
 /* The three launches a forward starts with in one (MVS4Net.py:60-76): mvster_pack_images (imgs -> packed),
  * mvster_relative_projection_multi (proj_matrices -> rt) and mvster_init_range (depth_values [B,ndv] -> hypo [B,D,h,w], the
  * first stage's hypotheses; h*w <= H*W).  Same arithmetic as the three, bit for bit. */

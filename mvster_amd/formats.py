@@ -155,12 +155,80 @@ def _admissible_size(h, w, max_h, max_w, base=64):
     return 1.0 * w // base * base, 1.0 * h // base * base
 
 
+def scale_input_size(h, w, max_h, max_w):
+    """The loader's target size for an ``h`` x ``w`` image within ``max_h`` x ``max_w`` (general_eval4.py:92-103) ->
+    ``(Hd, Wd, scale_h, scale_w)``: ints and the two Python floats the intrinsics are multiplied by.  Float arithmetic as
+    there: 1200 x 1600 within 864 x 1152 gives 832 x 1152 (0.72 * 1200 = 864 = 13.5 * 64, rounded down), the size the
+    reference runs DTU at."""
+    new_w, new_h = _admissible_size(h, w, max_h, max_w)
+    return int(new_h), int(new_w), 1.0 * new_h / h, 1.0 * new_w / w
+
+
+def scale_intrinsics(K, scale_h, scale_w):
+    """A copy of the float32 intrinsics ``K`` [3,3] or [V,3,3] with row 0 times ``scale_w`` and row 1 times ``scale_h``
+    (general_eval4.py:104-105: two in-place multiplications of a float32 matrix by a Python float)."""
+    K = np.array(K, dtype=np.float32)
+    K[..., 0, :] *= scale_w
+    K[..., 1, :] *= scale_h
+    return K
+
+
+def _axis_table(ns, nd):
+    """xofs / alpha of OpenCV's resize.cpp (INTER_LINEAR, float path) for one axis: ns source -> nd output samples."""
+    inv = np.float64(nd) / np.float64(ns)
+    scale = np.float64(1.0) / inv                                            # two roundings, not ns / nd
+    f = ((np.arange(nd, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int32)
+    f = f - s.astype(np.float32)
+    low, high = s < 0, s >= ns - 1
+    s[low], f[low] = 0, 0.0
+    s[high], f[high] = ns - 1, 0.0                                           # (the second tap is not read there)
+    return s, f.astype(np.float32)
+
+
+def resize_tables(Hs, Ws, Hd, Wd):
+    """Per-axis tap tables of ``cv2.resize(img [Hs,Ws], (Wd, Hd))``, INTER_LINEAR -> ``(sx, fx, sy, fy)``: first tap (int32)
+    and fraction (float32) per output column / row; the weights are ``1.f - f`` and ``f``.  Built once per size pair on
+    the host, in double precision, as OpenCV builds them before it touches a pixel; the GPU kernel gets them uploaded."""
+    sx, fx = _axis_table(int(Ws), int(Wd))
+    sy, fy = _axis_table(int(Hs), int(Hd))
+    return sx, fx, sy, fy
+
+
+def resize_linear(img, Hd, Wd):
+    """``cv2.resize(img, (Wd, Hd))`` with default arguments for a float32 [Hs,Ws,C] image (OpenCV's resize.cpp, float path,
+    restated; csrc/resize_math.h is the same arithmetic on the GPU): horizontal pass, then vertical, every product and
+    sum rounded to float32 on its own; the 2 x 2 mean of the area path at exactly 2:1 on both axes.  There is no
+    ``cv2`` to pin this against: agreement with a particular OpenCV binary is to within the last place of single results
+    (its SIMD builds may fuse the vertical pass) and has not been measured."""
+    img = np.asarray(img)
+    if img.dtype != np.float32 or img.ndim != 3:
+        raise RuntimeError("resize_linear: expects a float32 [H,W,C] image, got %s %s" % (img.dtype, img.shape))
+    Hs, Ws = img.shape[:2]
+    Hd, Wd = int(Hd), int(Wd)
+    if not (0 < Hd <= Hs and 0 < Wd <= Ws):
+        raise RuntimeError("resize_linear: %dx%d -> %dx%d: the loader never enlarges" % (Hs, Ws, Hd, Wd))
+    if Ws == 2 * Wd and Hs == 2 * Hd:
+        return ((img[0::2, 0::2] + img[0::2, 1::2]) + (img[1::2, 0::2] + img[1::2, 1::2])) * np.float32(0.25)
+    sx, fx, sy, fy = resize_tables(Hs, Ws, Hd, Wd)
+    sx1, sy1 = np.minimum(sx + 1, Ws - 1), np.minimum(sy + 1, Hs - 1)        # (weight 0 where the clamp acts)
+    one = np.float32(1.0)
+    a0, a1 = (one - fx)[None, :, None], fx[None, :, None]
+    b0, b1 = (one - fy)[:, None, None], fy[:, None, None]
+    t0 = img[sy][:, sx] * a0 + img[sy][:, sx1] * a1
+    t1 = img[sy1][:, sx] * a0 + img[sy1][:, sx1] * a1
+    return t0 * b0 + t1 * b1
+
+
 def load_eval_sample(datapath, scan, ref_view, src_views, nviews, interval_scale=1.06, ndepths=192,
-                     max_h=None, max_w=None):
+                     max_h=None, max_w=None, resample=False):
     """One evaluation sample as ``general_eval4.MVSDataset.__getitem__`` (:111-188) hands it to the forward pass:
     ``imgs`` list of [3,H,W] float32, ``proj_matrices`` dict stage1..4 of [N,2,4,4], ``depth_values`` [ndepths],
-    ``filename`` pattern.  Images must already have an admissible size (H, W multiples of 64 within max_h x max_w):
-    image resampling is outside the path and raises."""
+    ``filename`` pattern.  With the default ``resample=False`` images must already have an admissible size (H, W
+    multiples of 64 within max_h x max_w) and anything else raises.  ``resample=True``: images are brought to the
+    loader's size with ``resize_linear`` and the intrinsics scaled, as ``scale_mvs_input`` does, for samples whose views
+    share one native size (the reference's second resampling of a source to its reference view's size is not done:
+    DESIGN.md section 7)."""
     imgs, intr, extr, depth_values = [], [], [], None
     first_hw = None
     for i, vid in enumerate([ref_view] + list(src_views[:nviews - 1])):
@@ -172,7 +240,13 @@ def load_eval_sample(datapath, scan, ref_view, src_views, nviews, interval_scale
             os.path.join(datapath, "{}/cams/{:0>8}_cam.txt".format(scan, vid)), interval_scale, ndepths)
         h, w = img.shape[:2]
         new_w, new_h = _admissible_size(h, w, h if max_h is None else max_h, w if max_w is None else max_w)
-        if (new_h, new_w) != (h, w) or (first_hw is not None and (h, w) != first_hw):
+        if resample:
+            if first_hw is not None and (h, w) != first_hw:
+                raise NotImplementedError("image %s is %dx%d but the sample's reference view is %dx%d: views of different "
+                                          "native sizes within a scan are not supported" % (img_file, h, w, *first_hw))
+            if (new_h, new_w) != (h, w):
+                img = resize_linear(img, int(new_h), int(new_w))
+        elif (new_h, new_w) != (h, w) or (first_hw is not None and (h, w) != first_hw):
             raise NotImplementedError("image %s is %dx%d and would be resampled to %dx%d: resize the images first"
                                       % (img_file, h, w, *(first_hw or (new_h, new_w))))
         K[0, :] *= 1.0 * new_w / w

@@ -87,6 +87,36 @@ def pack_images_u8(imgs_u8):
     return out
 
 
+def resize_pack_images_u8(imgs_u8, Hd, Wd, want_u8=False):
+    """uint8 [V,Hs,Ws,3] -> [V,1,Hd,Wd,4] channels-last RGB0 float32: ``pack_images_u8`` with the evaluation loader's input
+    scaling (``cv2.resize`` with default arguments on ``read_img``'s floats; ``formats.resize_linear`` is the same
+    arithmetic on the host) in the same launch, for all images of a scan.  ``want_u8``: also the resized images as uint8
+    [V,Hd,Wd,3] = trunc(clip(x * 255, 0, 255)) -> (packed, u8).  ``Hd``, ``Wd``: multiples of 64, not larger than the
+    source.  The tap tables are built here (``formats.resize_tables``) and uploaded as one small buffer."""
+    import numpy as np
+    from . import formats
+    if not torch.is_tensor(imgs_u8) or not imgs_u8.is_cuda:
+        raise RuntimeError("mvster_amd.ops.resize_pack_images_u8: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[3] != 3:
+        raise RuntimeError("resize_pack_images_u8: expects uint8 [V,H,W,3], got %s %s" % (imgs_u8.dtype, tuple(imgs_u8.shape)))
+    x = imgs_u8.contiguous()
+    V, Hs, Ws, _ = x.shape
+    Hd, Wd = int(Hd), int(Wd)
+    if V < 1 or Hs < 1 or Ws < 1 or x.data_ptr() % 4:
+        raise RuntimeError("resize_pack_images_u8: empty or misaligned image stack %s" % (tuple(x.shape),))
+    if Hd < 64 or Wd < 64 or Hd % 64 or Wd % 64 or Hd > Hs or Wd > Ws:
+        raise RuntimeError("resize_pack_images_u8: target size %dx%d for %dx%d images: H and W must be positive multiples of 64 "
+                           "and not larger than the source (the loader never enlarges)" % (Hd, Wd, Hs, Ws))
+    sx, fx, sy, fy = formats.resize_tables(Hs, Ws, Hd, Wd)
+    words = np.concatenate([sx.view(np.int32), fx.view(np.int32), sy.view(np.int32), fy.view(np.int32)])
+    tables = torch.from_numpy(words).to(x.device)
+    out = torch.empty(V, 1, Hd, Wd, 4, device=x.device, dtype=torch.float32)
+    u8 = torch.empty(V, Hd, Wd, 3, device=x.device, dtype=torch.uint8) if want_u8 else None
+    _lib.check(_lib.load().mvster_resize_pack_images_u8(_ptr(x), _ptr(tables), _ptr(out), _ptr(u8), V, Hs, Ws, Hd, Wd, _stream()),
+               "resize_pack_images_u8")
+    return (out, u8) if want_u8 else out
+
+
 def forward_prologue(imgs, proj_list, depth_values, D, h, w, inverse):
     """``pack_images`` + ``relative_projection_multi`` + ``init_range`` (the first stage's hypotheses [B,D,h,w]) in one
     launch -> (packed, rt, hypo); the same bits as the three calls."""

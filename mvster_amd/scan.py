@@ -16,8 +16,12 @@ What the loop recomputes and this path does not:
 * The maps stay on the device: ``reconstruct_scan`` hands them to ``fusion.fuse_scene`` where they are.
 
 Same kernels on the same operands as ``model(imgs, proj_matrices, depth_values)`` per sample: ``depth`` and
-``photometric_confidence`` are bit-equal to it (tests/test_gpu_scan.py).  Image resampling stays outside the path
-(DESIGN.md section 7): all images of a scan must have one admissible size.
+``photometric_confidence`` are bit-equal to it (tests/test_gpu_scan.py).
+
+Scans at their native image size (``max_h`` / ``max_w``): the loader's input scaling
+(``general_eval4.MVSDataset.scale_mvs_input``) runs in the launch that packs the 8-bit images
+(``ops.resize_pack_images_u8``), the intrinsics are scaled on the host.  Without these arguments all images of a scan
+must have one admissible size.
 """
 import collections
 import os
@@ -91,14 +95,20 @@ def store_bytes(V, H, W, base_channels=8):
     return V * (H * W * c + (H // 2) * (W // 2) * 2 * c + (H // 4) * (W // 4) * 4 * c + (H // 8) * (W // 8) * 8 * c) * 4
 
 
-def _check_images(images):
-    """-> ("u8", [V,H,W,3]) or ("f32", [V,3,H,W]) as given (array or tensor, not copied), after the shape checks."""
+def _check_images(images, scaling=False):
+    """-> ("u8", [V,H,W,3]) or ("f32", [V,3,H,W]) as given (array or tensor, not copied), after the shape checks.
+    ``scaling``: the caller brings the images to an admissible size (``_scaled_inputs``), so any one common size passes."""
     if not torch.is_tensor(images) and not isinstance(images, np.ndarray):
         images = list(images)
         if not images:
             raise RuntimeError("infer_scan: no images")
         first = tuple(images[0].shape)
         for i, im in enumerate(images):
+            if tuple(im.shape) != first and scaling:
+                raise RuntimeError("infer_scan: image %d is %s but image 0 is %s: views of different native sizes within a "
+                                   "scan are not supported (the reference resamples each source view to its reference "
+                                   "view's size, so one image would need a level-store entry per partner size)"
+                                   % (i, tuple(im.shape), first))
             if tuple(im.shape) != first:
                 raise RuntimeError("infer_scan: image %d is %s but image 0 is %s: all views of a scan must have one size "
                                    "(resize the images first)" % (i, tuple(im.shape), first))
@@ -116,17 +126,33 @@ def _check_images(images):
         H, W = images.shape[2], images.shape[3]
     else:
         raise RuntimeError("infer_scan: images must be uint8 [V,H,W,3] or float32 [V,3,H,W], got %s" % (dt,))
+    if scaling and H > 0 and W > 0:
+        return kind, images, int(images.shape[0]), int(H), int(W)
     if H % 64 or W % 64 or H == 0 or W == 0:
         raise RuntimeError("infer_scan: image size %dx%d: H and W must be multiples of 64 (resampling stays outside the "
                            "path: resize the images first)" % (H, W))
     return kind, images, int(images.shape[0]), int(H), int(W)
 
 
+def _scaled_inputs(kind, H, W, Ks, max_h, max_w):
+    """The loader's target size and intrinsics for ``H`` x ``W`` images within ``max_h`` x ``max_w`` (``None``: that side
+    is not limited) -> (Hd, Wd, scaled copy of ``Ks``)."""
+    Hd, Wd, scale_h, scale_w = formats.scale_input_size(H, W, H if max_h is None else max_h, W if max_w is None else max_w)
+    if Hd < 64 or Wd < 64:
+        raise RuntimeError("infer_scan: image size %dx%d within max_h = %s, max_w = %s gives %dx%d: nothing is left after "
+                           "rounding down to multiples of 64" % (H, W, max_h, max_w, Hd, Wd))
+    if kind == "f32" and (Hd, Wd) != (H, W):
+        raise RuntimeError("infer_scan: float32 images of %dx%d would be resampled to %dx%d, which is done for uint8 images "
+                           "only: pass the decoded 8-bit images as uint8 [V,H,W,3]" % (H, W, Hd, Wd))
+    return Hd, Wd, formats.scale_intrinsics(Ks, scale_h, scale_w)
+
+
 class ScanResult(dict):
     """What ``infer_scan`` returns: ``ref_views`` [R] (view numbers, host), ``depth`` and ``photometric_confidence`` [R,H,W]
     on the GPU, ``Ks`` [V,3,3] / ``Es`` [V,4,4] at output resolution (the stage-4 camera ``write_cam`` gets in the
     reference), ``pairs`` (reference views with sources, full source lists: what fusion reads), ``view_ids`` (file
-    numbers of the views), ``stats`` (``fpn_runs``, ``replays``, ``captured``) and whatever else ``keep`` named."""
+    numbers of the views), ``stats`` (``fpn_runs``, ``replays``, ``captured``) and whatever else ``keep`` named.  With ``max_h`` / ``max_w``:
+    ``images``, the resized uint8 images [V,H,W,3] on the GPU, and ``Ks`` from the scaled intrinsics."""
 
     def timings(self):
         """Milliseconds per phase (HIP events recorded by ``infer_scan``; synchronises)."""
@@ -219,12 +245,13 @@ def _runner(model, V, H, W, nviews, ndv):
     return hit[1]
 
 
-def _run_fpn(model, runner, kind, dev_images, chunk):
+def _run_fpn(model, runner, kind, dev_images, chunk, packed=None):
     """The FPN plan over the distinct images, ``chunk`` at a time (last chunk padded by repeating its last image), each
-    level into its store.  -> number of plan runs."""
+    level into its store.  ``packed``: the RGB0 stack where the caller has made it already.  -> number of plan runs."""
     fpn = runner.plans[0]
     V = runner.V
-    packed = ops.pack_images_u8(dev_images) if kind == "u8" else None        # [V,1,H,W,4], one launch for the scan
+    if packed is None and kind == "u8":
+        packed = ops.pack_images_u8(dev_images)                              # [V,1,H,W,4], one launch for the scan
     runs = 0
     for a in range(0, V, chunk):
         b = min(V, a + chunk)
@@ -243,7 +270,8 @@ def _run_fpn(model, runner, kind, dev_images, chunk):
 
 @torch.no_grad()
 def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2,
-               keep=("depth", "photometric_confidence"), ndepths=192, fpn_chunk=None, max_store_bytes=None, view_ids=None):
+               keep=("depth", "photometric_confidence"), ndepths=192, fpn_chunk=None, max_store_bytes=None, view_ids=None,
+               max_h=None, max_w=None):
     """Depth and confidence maps of all reference views of a scan.
 
     ``images``: uint8 [V,H,W,3] (NumPy, or a tensor on the GPU) or float32 [V,3,H,W] in 0..1, or a sequence of per-view
@@ -257,10 +285,24 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     to return as [R,...] stacks -- last-stage names (``"depth"``) or ``"stage2.depth"``; after each replay only these
     are copied out of the graph's static outputs.  ``fpn_chunk``: images per FPN run (default ``nviews``: the
     per-sample batch, the only value that carries the bit-equality with the per-sample forward).  ``max_store_bytes``:
-    raise if the level stores (``store_bytes``) would exceed it.  -> ScanResult."""
-    kind, images, V, H, W = _check_images(images)
+    raise if the level stores (``store_bytes``) would exceed it.
+
+    ``max_h`` / ``max_w`` (both ``None``: nothing below applies): the reference loader's input scaling
+    (``general_eval4.MVSDataset.scale_mvs_input``, e.g. 864 / 1152 for DTU).  uint8 images of any one common size are
+    shrunk to fit, rounded down to multiples of 64 and resampled on the GPU in the launch that packs them
+    (``ops.resize_pack_images_u8``); ``Ks`` is scaled to match, and it is the scaled intrinsics the result carries.  The
+    result's ``images`` are the resized uint8 images on the GPU (``write_scan_outputs`` and ``reconstruct_scan`` take
+    them).  The source stack is extra device memory until the FPN has run -- ``V * Hs * Ws * 3`` bytes, 282 MB for 49
+    views of 1200 x 1600 -- and counts towards ``max_store_bytes``.  float32 images that would need resampling and views
+    of different native sizes raise.  -> ScanResult."""
+    scaling = max_h is not None or max_w is not None
+    kind, images, V, H, W = _check_images(images, scaling)
     if len(Ks) != V or len(Es) != V:
         raise RuntimeError("infer_scan: %d images for %d intrinsics and %d extrinsics" % (V, len(Ks), len(Es)))
+    Hs, Ws = H, W
+    if scaling:
+        H, W, Ks = _scaled_inputs(kind, Hs, Ws, Ks, max_h, max_w)
+    resize = scaling and kind == "u8"
     plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths)
     if in_flight < 1:
         raise RuntimeError("infer_scan: in_flight = %d" % in_flight)
@@ -268,6 +310,11 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     if not 1 <= chunk <= 16:
         raise RuntimeError("infer_scan: fpn_chunk = %d (1..16 images per FPN run)" % chunk)
     need = store_bytes(V, H, W, model.feature.out_channels[-1])
+    source_bytes = V * Hs * Ws * 3 if resize else 0
+    if max_store_bytes is not None and resize and need + source_bytes > max_store_bytes:
+        raise RuntimeError("infer_scan: the level stores of %d views of %dx%d and the %dx%d source images need %d + %d bytes "
+                           "(%.2f GB), more than max_store_bytes = %d"
+                           % (V, H, W, Hs, Ws, need, source_bytes, (need + source_bytes) / 1e9, max_store_bytes))
     if max_store_bytes is not None and need > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d need %d bytes (%.2f GB), more than "
                            "max_store_bytes = %d" % (V, H, W, need, need / 1e9, max_store_bytes))
@@ -294,7 +341,11 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
         ev["upload"][1].record(main)
 
         ev["fpn"][0].record(main)
-        fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk)
+        packed = small = None
+        if resize:
+            packed, small = ops.resize_pack_images_u8(dev_images, H, W, want_u8=True)
+        fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk, packed)
+        del dev_images, packed                                               # (the source stack goes back to the allocator)
         ev["fpn"][1].record(main)
 
         # [K,R,...] stacks of the kept maps; same-shaped ones share one allocation (one staging copy moves them all)
@@ -340,6 +391,9 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
                      Ks=k4[:, 1, :3, :3].copy(), Es=k4[:, 0].copy(),
                      view_ids=list(range(V)) if view_ids is None else [int(v) for v in view_ids],
                      stats={"fpn_runs": fpn_runs, "replays": R, "captured": captured_now, "store_bytes": need}, events=ev)
+    if resize:
+        res["images"] = small
+        res["stats"]["source_bytes"] = source_bytes
     for name, st in zip(keep, stacks):
         res[name] = st
     res.maps, res.map_names = maps, keep
@@ -387,20 +441,24 @@ def read_scan_folder(datapath, scan, interval_scale=1.06, ndepths=192):
                 pairs=[(slot[r], [slot[v] for v in srcs]) for r, srcs in file_pairs])
 
 
-def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192):
-    """Host planning of ``infer_scan_folder`` -> (the ``read_scan_folder`` dict, ScanPlan); no device work."""
+def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, max_h=None, max_w=None):
+    """Host planning of ``infer_scan_folder`` -> (the ``read_scan_folder`` dict, ScanPlan); no device work.  With ``max_h`` /
+    ``max_w`` the plan is made from the scaled intrinsics (the dict keeps the files' own)."""
     sc = read_scan_folder(datapath, scan, interval_scale, ndepths)
-    _check_images(sc["images"])
-    return sc, plan_scan(sc["Ks"], sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths)
+    scaling = max_h is not None or max_w is not None
+    kind, _, _, H, W = _check_images(sc["images"], scaling)
+    Ks = _scaled_inputs(kind, H, W, sc["Ks"], max_h, max_w)[2] if scaling else sc["Ks"]
+    return sc, plan_scan(Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths)
 
 
 def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, **kw):
     """``infer_scan`` on a scan folder in the reference's layout (``general_eval4.MVSDataset``).  The result's
-    ``ref_views`` / ``pairs`` index ``view_ids`` (the file numbers)."""
+    ``ref_views`` / ``pairs`` index ``view_ids`` (the file numbers).  ``max_h`` / ``max_w`` (the loader's arguments) go
+    through to ``infer_scan``: a scan is taken at its native image size, as the dataset ships it."""
     sc = read_scan_folder(datapath, scan, interval_scale, ndepths)
     res = infer_scan(model, sc["images"], sc["Ks"], sc["Es"], sc["depth_ranges"], sc["pairs"], nviews=nviews,
                      ndepths=ndepths, view_ids=sc["view_ids"], **kw)
-    res["images"] = sc["images"]
+    res.setdefault("images", sc["images"])                                  # (the resized ones where infer_scan scaled)
     return res
 
 
@@ -454,12 +512,15 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     ``ScanResult`` as its ``scan`` attribute); writes the point cloud to ``plyfilename`` if given.
 
     Every source view a reference view's pair lists must have a depth map of its own, i.e. be a reference view with
-    sources itself (the reference's ``filter_depth`` reads its ``depth_est`` file).  Colours come from the INPUT images,
-    not from the re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same,
-    colours differ by the JPEG re-encoding the reference adds."""
+    sources itself (the reference's ``filter_depth`` reads its ``depth_est`` file).  Colours come from the INPUT images
+    (with ``max_h`` / ``max_w``: from the resized ones, the pixels the reference writes to ``images/``), not from the
+    re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same, colours differ
+    by the JPEG re-encoding the reference adds."""
     from . import fusion
-    kind, images, V, H, W = _check_images(images)
+    kind, images, V, H, W = _check_images(images, kw.get("max_h") is not None or kw.get("max_w") is not None)
     scan = infer_scan(model, images, Ks, Es, depth_ranges, pairs, **kw)
+    if torch.is_tensor(scan.get("images")):
+        kind, images = "u8", scan["images"]                                  # uint8 [V,Hd,Wd,3], already on the device
     slot = {int(r): i for i, r in enumerate(scan["ref_views"])}
     fpairs = []
     for r, srcs in scan["pairs"]:
