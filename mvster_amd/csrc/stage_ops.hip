@@ -890,6 +890,94 @@ __global__ void __launch_bounds__(256) resize_pack_images_u8_kernel(const unsign
     }
 }
 
+// The Tanks and Temples / ETH3D loaders' image preparation (datasets/tanks.py:53-60: a crop; datasets/eth3d.py:57-62: every
+// view resized to one img_wh from its OWN native size) fused into the 8-bit pack, for all views of a scan in one launch:
+// resize_pack_images_u8_kernel with per-view addressing.  buf = one ragged byte buffer of the decoded images; desc = per view
+// LOAD_PACK_DESC_WORDS 32-bit words (include/mvster_hip.h): byte offset of the image (low, high word), native Hs, Ws, the
+// source window y0, x0, hw, ww, the word offset of the window size's tap tables in `tabs` (laid out as for
+// resize_pack_images_u8_kernel, indices relative to the window), the area flag.  blockIdx.y is the view, so the descriptor is
+// uniform over the workgroup: it is read once through the scalar cache, not per lane.  Hd * Wd / 4 is a multiple of 1024
+// (both are multiples of 64), so blockIdx.x covers a view's groups of four pixels exactly.
+// A window that already has the output size (a pure crop; Tanks always) takes no taps: 12 source bytes per thread, as
+// pack_images_u8_kernel reads them.  Their address is 3 * ((y0 + y) * Ws + x0) + 12 * xq behind a 16-byte aligned image, so
+// it is 4-byte aligned for every lane only where the window's first byte and the row pitch 3 * Ws both are; a lane takes the
+// three dword loads where its own address is aligned and twelve byte loads otherwise -- the same bytes either way.
+// Arithmetic: resize_math.h, unchanged.  Tap indices are clamped into the window (a bad table: wrong pixels, no read
+// outside the window); the windows themselves are checked on the host before the launch.
+constexpr int LOAD_PACK_DESC_WORDS = 12;
+
+template <bool U8>
+__global__ void __launch_bounds__(256) load_pack_images_u8_kernel(const unsigned char* __restrict__ buf, const int* __restrict__ desc,
+                                                                  const int* __restrict__ tabs, float* __restrict__ out,
+                                                                  unsigned char* __restrict__ out_u8, int Hd, int Wd) {
+    const unsigned v = blockIdx.y;
+    const int* d = desc + v * LOAD_PACK_DESC_WORDS;
+    const long off = (long)(((unsigned long)(unsigned)d[1] << 32) | (unsigned)d[0]);
+    const int Ws = d[3], hw = d[6], ww = d[7];
+    const long pitch = (long)Ws * 3;
+    const unsigned char* win = buf + off + ((long)d[4] * Ws + d[5]) * 3;     // first byte of the window
+    const unsigned q = blockIdx.x * 256u + threadIdx.x;              // group of four pixels of this view
+    const unsigned wq = (unsigned)Wd >> 2;
+    const unsigned y = q / wq, xq = q - y * wq;
+    const mv::Recip k255 = mv::make_recip(255.0f);
+    const long p0 = ((long)v * Hd + y) * Wd + xq * 4;
+    unsigned char by[12];
+    if (hw == Hd && ww == Wd) {
+        const unsigned char* p = win + y * pitch + xq * 12;
+        unsigned char s[12];
+        if (((uintptr_t)p & 3) == 0) {
+            const unsigned* w = reinterpret_cast<const unsigned*>(p);
+            const unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s[j] = (unsigned char)(w0 >> (8 * j));
+                s[4 + j] = (unsigned char)(w1 >> (8 * j));
+                s[8 + j] = (unsigned char)(w2 >> (8 * j));
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) s[j] = p[j];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float r = rsz::level(s[3 * k], k255), g = rsz::level(s[3 * k + 1], k255), b = rsz::level(s[3 * k + 2], k255);
+            st4(out + (p0 + k) * 4, (f32x4){r, g, b, 0.0f});
+            if (U8) {
+                by[3 * k] = rsz::to_u8(r);
+                by[3 * k + 1] = rsz::to_u8(g);
+                by[3 * k + 2] = rsz::to_u8(b);
+            }
+        }
+    } else {
+        const int* tab = tabs + d[8];
+        const bool area = d[9] != 0;
+        const int y0 = mv::clampi(tab[2 * Wd + y], hw - 1), y1 = rsz::tap1(y0, hw);
+        const float fy = __int_as_float(tab[2 * Wd + Hd + y]);
+        const unsigned char* r0 = win + y0 * pitch;
+        const unsigned char* r1 = win + y1 * pitch;
+        const int4 sx4 = *reinterpret_cast<const int4*>(tab + xq * 4);
+        const int4 fx4 = *reinterpret_cast<const int4*>(tab + Wd + xq * 4);
+        const int sx[4] = {sx4.x, sx4.y, sx4.z, sx4.w}, fxb[4] = {fx4.x, fx4.y, fx4.z, fx4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x0 = mv::clampi(sx[k], ww - 1);
+            float rgb[3];
+            rsz::pixel(r0, r1, x0, rsz::tap1(x0, ww), __int_as_float(fxb[k]), fy, area, k255, rgb);
+            st4(out + (p0 + k) * 4, (f32x4){rgb[0], rgb[1], rgb[2], 0.0f});
+            if (U8) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) by[3 * k + c] = rsz::to_u8(rgb[c]);
+            }
+        }
+    }
+    if (U8) {
+        unsigned* w = reinterpret_cast<unsigned*>(out_u8 + p0 * 3);  // 12 bytes per group: 4-byte aligned
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            w[j] = (unsigned)by[4 * j] | ((unsigned)by[4 * j + 1] << 8) | ((unsigned)by[4 * j + 2] << 16) | ((unsigned)by[4 * j + 3] << 24);
+    }
+}
+
 struct MultiProjArgs {
     const float* pm[8];     // per stage [B,N,2,4,4]
     float* rt;              // [nstage, B, N-1, 12]
@@ -1207,6 +1295,35 @@ extern "C" int mvster_resize_pack_images_u8(const unsigned char* imgs, const voi
     else
         hipLaunchKernelGGL(resize_pack_images_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, imgs, (const int*)tables, out,
                            out_u8, Hs, Ws, Hd, Wd, area, (unsigned)groups);
+    return mv_check_launch();
+}
+
+extern "C" int mvster_load_pack_images_u8(const unsigned char* buf, long buf_bytes, const int* desc_host, const int* desc,
+                                          const void* tables, long table_words, float* out, unsigned char* out_u8, int V, int Hd,
+                                          int Wd, void* stream) {
+    if (!buf || !desc_host || !desc || !out || (!tables && table_words != 0)) return MVSTER_ERR_NULL;
+    if (V <= 0 || V > 65535 || Hd <= 0 || Wd <= 0 || Hd % 64 || Wd % 64 || buf_bytes <= 0 || table_words < 0) return MVSTER_ERR_SHAPE;
+    if (((uintptr_t)buf & 15) || ((uintptr_t)desc & 3) || ((uintptr_t)tables & 15) || ((uintptr_t)out_u8 & 3)) return MVSTER_ERR_SHAPE;
+    const long blocks = (long)Hd * Wd / 1024;                        // 256 threads x 4 pixels; exact for multiples of 64
+    if (blocks > 0x7fffffffL) return MVSTER_ERR_SHAPE;
+    for (int v = 0; v < V; ++v) {                                    // the host copy of the descriptors: every address the kernel forms
+        const int* d = desc_host + (long)v * LOAD_PACK_DESC_WORDS;
+        const long off = (long)(((unsigned long)(unsigned)d[1] << 32) | (unsigned)d[0]);
+        const long Hs = d[2], Ws = d[3], y0 = d[4], x0 = d[5], hw = d[6], ww = d[7], tab = d[8];
+        if (off < 0 || (off & 15) || Hs <= 0 || Ws <= 0 || off > buf_bytes || Hs * Ws * 3 > buf_bytes - off) return MVSTER_ERR_SHAPE;
+        if (y0 < 0 || x0 < 0 || hw <= 0 || ww <= 0 || y0 + hw > Hs || x0 + ww > Ws) return MVSTER_ERR_SHAPE;   // window outside its image
+        if (Hd > hw || Wd > ww) return MVSTER_ERR_SHAPE;             // no path enlarges
+        if ((d[9] != 0) != (ww == 2L * Wd && hw == 2L * Hd)) return MVSTER_ERR_SHAPE;
+        if (hw == Hd && ww == Wd) continue;                          // a pure crop reads no table
+        if (tab < 0 || (tab & 3) || tab + 2L * Wd + 2L * Hd > table_words) return MVSTER_ERR_SHAPE;
+    }
+    const dim3 grid((unsigned)blocks, (unsigned)V);
+    if (out_u8)
+        hipLaunchKernelGGL(load_pack_images_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, buf, desc, (const int*)tables, out,
+                           out_u8, Hd, Wd);
+    else
+        hipLaunchKernelGGL(load_pack_images_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, buf, desc, (const int*)tables, out,
+                           out_u8, Hd, Wd);
     return mv_check_launch();
 }
 

@@ -4,7 +4,8 @@
 
 Behaviour follows the reference's readers and writers -- ``datasets/data_io.py:6-71`` (``read_pfm`` / ``save_pfm``),
 ``datasets/general_eval4.py:24-57`` (view list), ``:59-79`` (``read_cam_file``), ``:81-86`` (``read_img``), ``:92-108``
-(admissible image size), ``:111-188`` (sample), ``test_mvs4.py:94-103`` (``read_camera_parameters``), ``:126-136``
+(admissible image size), ``:111-188`` (sample), ``datasets/tanks.py`` / ``datasets/eth3d.py`` (``read_cam_file_minmax``,
+``load_tanks_sample``, ``load_eth3d_sample``: restated and compared in ``tests/test_scan_datasets_cpu.py``), ``test_mvs4.py:94-103`` (``read_camera_parameters``), ``:126-136``
 (``read_pair_file``), ``:138-155`` (``write_cam``).  **Pinned** by ``tests/golden/g10_formats.npz``: the bytes / text /
 arrays the reference's own functions write and read for the same inputs (``oracle/make_golden.py g10``), compared
 byte for byte and element for element in ``tests/test_formats_cpu.py``.
@@ -80,6 +81,18 @@ def read_cam_file(filename, interval_scale=1.0, ndepths=192):
         depth_max = depth_min + int(float(fields[2])) * depth_interval
         depth_interval = (depth_max - depth_min) / ndepths
     return intrinsics, extrinsics, depth_min, depth_interval * interval_scale
+
+
+def read_cam_file_minmax(filename, negative_min_to=None):
+    """The reader of the Tanks and Temples and ETH3D loaders (datasets/tanks.py:33-46, datasets/eth3d.py:40-55) ->
+    (intrinsics at FULL resolution, extrinsics, depth_min, depth_max): the first and the LAST number of line 11, whatever
+    lies between them (an interval, a plane count).  ``negative_min_to=1``: ETH3D's clamp, a negative depth_min becomes 1."""
+    intrinsics, extrinsics = read_camera_parameters(filename)
+    fields = _cam_lines(filename)[11].split()
+    depth_min, depth_max = float(fields[0]), float(fields[-1])
+    if negative_min_to is not None and depth_min < 0:
+        depth_min = negative_min_to
+    return intrinsics, extrinsics, depth_min, depth_max
 
 
 def write_cam(filename, cam):
@@ -173,6 +186,15 @@ def scale_intrinsics(K, scale_h, scale_w):
     return K
 
 
+def crop_intrinsics(K, top, left):
+    """A copy of the float32 intrinsics ``K`` [3,3] or [V,3,3] for an image that lost ``top`` rows and ``left`` columns:
+    ``cy - top``, ``cx - left`` (datasets/tanks.py:58: ``intrinsics[1,2] = intrinsics[1,2] - 28``, one float32 subtraction)."""
+    K = np.array(K, dtype=np.float32)
+    K[..., 1, 2] = K[..., 1, 2] - top
+    K[..., 0, 2] = K[..., 0, 2] - left
+    return K
+
+
 def _axis_table(ns, nd):
     """xofs / alpha of OpenCV's resize.cpp (INTER_LINEAR, float path) for one axis: ns source -> nd output samples."""
     inv = np.float64(nd) / np.float64(ns)
@@ -259,3 +281,54 @@ def load_eval_sample(datapath, scan, ref_view, src_views, nviews, interval_scale
             depth_values = depth_value_range(depth_min, depth_interval, ndepths)
     return {"imgs": imgs, "proj_matrices": stage_proj_matrices(intr, extr), "depth_values": depth_values,
             "filename": scan + "/{}/" + "{:0>8}".format(ref_view) + "{}"}
+
+
+def _quarter(K):
+    """Full-resolution intrinsics -> the quarter-resolution convention of ``read_cam_file`` / ``stage_proj_matrices`` (rows
+    0-1 divided by 4, exact).  ``stage_proj_matrices`` of it carries the bits of the Tanks / ETH3D loaders' chain
+    ``x 0.125, x 2, x 2, x 2`` (datasets/tanks.py:96-110): every factor is a power of two (tests/test_scan_datasets_cpu.py)."""
+    K = np.array(K, dtype=np.float32)
+    K[..., :2, :] /= 4.0
+    return K
+
+
+def _dataset_sample(datapath, scan, ref_view, src_views, nviews, cams, prepare, negative_min_to):
+    imgs, intr, extr, depth_values = [], [], [], None
+    for i, vid in enumerate([ref_view] + list(src_views[:nviews - 1])):     # cut, never padded (tanks.py:68)
+        img = read_img(os.path.join(datapath, scan, "images", "{:0>8}.jpg".format(vid)))
+        K, E, depth_min, depth_max = read_cam_file_minmax(os.path.join(datapath, scan, cams, "{:0>8}_cam.txt".format(vid)),
+                                                          negative_min_to)
+        K, img = prepare(K, img)
+        imgs.append(img.transpose(2, 0, 1))
+        intr.append(_quarter(K))
+        extr.append(E)
+        if i == 0:
+            depth_values = np.array([depth_min, depth_max], dtype=np.float32)
+    return {"imgs": imgs, "proj_matrices": stage_proj_matrices(intr, extr), "depth_values": depth_values,
+            "filename": scan + "/{}/" + "{:0>8}".format(ref_view) + "{}"}
+
+
+def load_tanks_sample(datapath, scan, ref_view, src_views, nviews=7, crop_rows=(28, 28)):
+    """One sample as ``datasets/tanks.py`` ``MVSDataset.__getitem__`` (:65-133) builds it from ``datapath/scan`` (the caller
+    joins the split): ``crop_rows = (top, bottom)`` rows cut off every image without resampling and ``cy - top`` (:53-60;
+    the loader's 1080 -> 1024), cameras from ``cams/``, ``depth_values`` = [depth_min, depth_max] of the reference view's
+    cam file, the source list cut to ``nviews - 1`` and never padded.  ``imgs`` list of [3,H,W] float32."""
+    top, bottom = int(crop_rows[0]), int(crop_rows[1])
+
+    def prepare(K, img):
+        return crop_intrinsics(K, top, 0), img[top:img.shape[0] - bottom, :, :]
+    return _dataset_sample(datapath, scan, ref_view, src_views, nviews, "cams", prepare, None)
+
+
+def load_eth3d_sample(datapath, scan, ref_view, src_views, nviews=7, img_wh=(1920, 1280)):
+    """One sample as ``datasets/eth3d.py`` ``MVSDataset.__getitem__`` (:67-135): every image resized to ``img_wh = (W, H)``
+    from its own native size (``resize_linear`` where the loader calls ``cv2.resize``) and its intrinsics scaled by its own
+    ``W / original_w``, ``H / original_h`` (:89-90), cameras from ``cams_1/``, a negative depth_min replaced by 1 (:51-52),
+    ``depth_values`` = [depth_min, depth_max].  Views of different native sizes are fine: the target does not depend on a
+    view's partners.  Enlarging raises, as ``resize_linear`` does."""
+    Wd, Hd = int(img_wh[0]), int(img_wh[1])
+
+    def prepare(K, img):
+        h, w = img.shape[:2]
+        return scale_intrinsics(K, Hd / h, Wd / w), resize_linear(img, Hd, Wd)
+    return _dataset_sample(datapath, scan, ref_view, src_views, nviews, "cams_1", prepare, 1)

@@ -117,6 +117,111 @@ def resize_pack_images_u8(imgs_u8, Hd, Wd, want_u8=False):
     return (out, u8) if want_u8 else out
 
 
+LOAD_PACK_DESC_WORDS = 12      # per-view descriptor of mvster_load_pack_images_u8 (include/mvster_hip.h)
+
+
+def load_pack_descriptors(sizes, Hd, Wd, crop=(0, 0, 0, 0)):
+    """Host side of ``load_pack_images_u8`` (pure NumPy): ``sizes`` = the views' native ``(Hs, Ws)``, ``crop`` = rows / columns
+    cut off at ``(top, bottom, left, right)`` of every view -> ``(desc, tables, total)``: the descriptors int32
+    [V, LOAD_PACK_DESC_WORDS] as include/mvster_hip.h lays them out, the tap-table words int32 (``formats.resize_tables`` of
+    window -> ``Hd`` x ``Wd``, built once per distinct window size and shared; a window that already has the output size has
+    none), and the length in bytes of the ragged buffer (every view starts on a multiple of 16).  Raises where the kernel's
+    entry point would return an error: ``Hd`` / ``Wd`` that are not positive multiples of 64, a crop that leaves nothing, a
+    window smaller than the output on either axis -- no path enlarges."""
+    import numpy as np
+    from . import formats
+    Hd, Wd = int(Hd), int(Wd)
+    top, bottom, left, right = [int(c) for c in crop]
+    if Hd < 64 or Wd < 64 or Hd % 64 or Wd % 64:
+        raise RuntimeError("load_pack_images_u8: target size %dx%d: H and W must be positive multiples of 64" % (Hd, Wd))
+    if min(top, bottom, left, right) < 0:
+        raise RuntimeError("load_pack_images_u8: crop = %s: negative" % ((top, bottom, left, right),))
+    desc = np.zeros((len(sizes), LOAD_PACK_DESC_WORDS), dtype=np.int32)
+    words, where, off, n = [], {}, 0, 0
+    for v, (Hs, Ws) in enumerate(sizes):
+        Hs, Ws = int(Hs), int(Ws)
+        hw, ww = Hs - top - bottom, Ws - left - right
+        if hw < Hd or ww < Wd:
+            raise RuntimeError("load_pack_images_u8: view %d is %dx%d, %dx%d after the crop %s, smaller than the target %dx%d: "
+                               "nothing here enlarges an image (the loaders never do)"
+                               % (v, Hs, Ws, max(hw, 0), max(ww, 0), (top, bottom, left, right), Hd, Wd))
+        tab = 0
+        if (hw, ww) != (Hd, Wd):
+            if (hw, ww) not in where:
+                where[(hw, ww)] = n
+                sx, fx, sy, fy = formats.resize_tables(hw, ww, Hd, Wd)
+                words += [sx.view(np.int32), fx.view(np.int32), sy.view(np.int32), fy.view(np.int32)]
+                n += 2 * Wd + 2 * Hd
+            tab = where[(hw, ww)]
+        desc[v, :2] = np.array([off], dtype="<i8").view(np.int32)            # low word, high word
+        desc[v, 2:10] = Hs, Ws, top, left, hw, ww, tab, int(ww == 2 * Wd and hw == 2 * Hd)
+        off += (Hs * Ws * 3 + 15) // 16 * 16
+    tables = np.concatenate(words) if words else np.zeros(0, dtype=np.int32)
+    return desc, tables, off
+
+
+def load_pack_images_u8(views, Hd, Wd, crop=(0, 0, 0, 0), want_u8=False, device=None):
+    """The image preparation of the reference's Tanks and Temples and ETH3D loaders for all views of a scan in one launch:
+    ``views`` = a sequence of uint8 [Hs_i,Ws_i,3] arrays or tensors (host or GPU; their native sizes may differ) ->
+    [V,1,Hd,Wd,4] channels-last RGB0 float32.  Each view is cropped by ``crop = (top, bottom, left, right)`` and the window
+    that remains resized to ``Hd`` x ``Wd`` with its own factors, in the arithmetic of ``resize_pack_images_u8`` (per view
+    ``formats.resize_linear(u8 / 255)`` of the window, bit for bit; the 2 x 2 mean where a window is exactly twice the output
+    on both axes).  A window that already has the output size (``datasets/tanks.py``: 1080 rows minus 28 + 28) is only
+    converted: the bits of ``pack_images_u8`` on the slices.  ``want_u8``: also uint8 [V,Hd,Wd,3] as ``resize_pack_images_u8``
+    gives them -> (packed, u8).  **No path enlarges**: a window smaller than ``Hd`` x ``Wd`` on either axis raises, as do
+    ``Hd`` / ``Wd`` that are not positive multiples of 64.
+
+    Host views go into one ragged buffer and up in ONE copy; descriptors and tap tables (``load_pack_descriptors``) in one more.
+    A contiguous GPU stack [V,Hs,Ws,3] whose views start on multiples of 16 bytes is read where it lies."""
+    import numpy as np
+    if torch.is_tensor(views) or isinstance(views, np.ndarray):
+        views = views if views.ndim == 4 else [views]
+    stack = views if torch.is_tensor(views) else None
+    views = list(views)
+    if not views:
+        raise RuntimeError("load_pack_images_u8: no views")
+    for i, im in enumerate(views):
+        if im.dtype not in (torch.uint8, np.dtype(np.uint8)) or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise RuntimeError("load_pack_images_u8: view %d: expects uint8 [H,W,3], got %s %s" % (i, im.dtype, tuple(im.shape)))
+    desc, tables, total = load_pack_descriptors([im.shape[:2] for im in views], Hd, Wd, crop)
+    V, Hd, Wd = len(views), int(Hd), int(Wd)
+    if V > 65535:
+        raise RuntimeError("load_pack_images_u8: %d views (at most 65535 in one launch)" % V)
+    if device is None:
+        on_gpu = [im.device for im in views if torch.is_tensor(im) and im.is_cuda]
+        device = on_gpu[0] if on_gpu else "cuda"
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("mvster_amd.ops.load_pack_images_u8 runs on the GPU only (the HIP path has no CPU fallback)")
+    offs = (desc[:, 0].astype(np.int64) & 0xffffffff) | (desc[:, 1].astype(np.int64) << 32)
+    per = views[0].shape[0] * views[0].shape[1] * 3
+    if (stack is not None and stack.is_cuda and stack.device == device and stack.is_contiguous() and per % 16 == 0
+            and stack.data_ptr() % 16 == 0):
+        buf = stack.reshape(-1)                                               # (equal sizes at a pitch of 16: the offsets hold)
+    elif any(torch.is_tensor(im) and im.is_cuda for im in views):
+        buf = torch.empty(total, dtype=torch.uint8, device=device)
+        for im, o in zip(views, offs):
+            im = im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))
+            buf[o:o + im.numel()].copy_(im.reshape(-1))
+    else:
+        host = np.empty(total, dtype=np.uint8)
+        for im, o in zip(views, offs):
+            im = im.numpy() if torch.is_tensor(im) else im
+            host[o:o + im.size] = im.reshape(-1)
+        buf = torch.from_numpy(host).to(device)
+    # descriptors (V * 12 words: a multiple of 4, so the tables behind them stay 16-byte aligned) and tables: one upload
+    blob_host = np.concatenate([desc.reshape(-1), tables])
+    blob = torch.from_numpy(blob_host).to(device)
+    ntab = int(tables.size)
+    out = torch.empty(V, 1, Hd, Wd, 4, device=device, dtype=torch.float32)
+    u8 = torch.empty(V, Hd, Wd, 3, device=device, dtype=torch.uint8) if want_u8 else None
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().mvster_load_pack_images_u8(_ptr(buf), buf.numel(), desc.ctypes.data, _ptr(blob),
+                                                          blob.data_ptr() + desc.size * 4 if ntab else None, ntab, _ptr(out),
+                                                          _ptr(u8), V, Hd, Wd, _stream()), "load_pack_images_u8")
+    return (out, u8) if want_u8 else out
+
+
 def forward_prologue(imgs, proj_list, depth_values, D, h, w, inverse):
     """``pack_images`` + ``relative_projection_multi`` + ``init_range`` (the first stage's hypotheses [B,D,h,w]) in one
     launch -> (packed, rt, hypo); the same bits as the three calls."""

@@ -22,6 +22,10 @@ Scans at their native image size (``max_h`` / ``max_w``)
 (``general_eval4.MVSDataset.scale_mvs_input``) runs in the launch that packs the 8-bit images
 (``ops.resize_pack_images_u8``), the intrinsics are scaled on the host.  Without these arguments all images of a scan
 must have one admissible size.
+
+The reference's two other evaluation loaders (``crop_rows`` = ``datasets/tanks.py``, ``img_wh`` = ``datasets/eth3d.py``,
+``depth_range_kind="min_max"`` for both): a crop, or a resize of every view from its own native
+size to one target, in the launch that packs the 8-bit images (``ops.load_pack_images_u8``).
 """
 import collections
 import os
@@ -50,12 +54,20 @@ def _as_pairs(pairs, V):
     return out
 
 
-def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192):
+DEPTH_RANGE_KINDS = ("min_interval", "min_max")
+
+
+def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192, depth_range_kind="min_interval"):
     """Per-view quarter-resolution intrinsics ``Ks`` [V,3,3] and extrinsics ``Es`` [V,4,4] (``formats.read_cam_file``),
     ``depth_ranges`` [V] of (depth_min, depth_interval) or ready ``depth_values`` [V,ndv], ``pairs`` as
     ``formats.read_pair_file`` -> ScanPlan.  View list per reference view as ``formats.eval_view_list`` +
     ``formats.load_eval_sample``: sources cut to ``nviews - 1``, short lists padded by repeating the first source,
-    reference views without sources dropped."""
+    reference views without sources dropped.  ``depth_range_kind="min_max"``: ``depth_ranges`` [V,2] holds (depth_min,
+    depth_max), the two values ``datasets/tanks.py:131`` and ``datasets/eth3d.py:133`` hand to the forward, and goes through
+    as a sample's ``depth_values`` (ndv = 2) -- the forward reads the first and the last entry and the count, so this is a
+    different input from the 192 values the default builds, not a shorthand for them."""
+    if depth_range_kind not in DEPTH_RANGE_KINDS:
+        raise RuntimeError("infer_scan: depth_range_kind = %r (one of %s)" % (depth_range_kind, ", ".join(DEPTH_RANGE_KINDS)))
     Ks = np.asarray(Ks, dtype=np.float32)
     Es = np.asarray(Es, dtype=np.float32)
     V = len(Ks)
@@ -65,6 +77,9 @@ def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192):
         raise RuntimeError("infer_scan: nviews = %d (at least one source view is needed)" % nviews)
     pairs = _as_pairs(pairs, V)
     dr = np.asarray(depth_ranges, dtype=np.float32)
+    if depth_range_kind == "min_max" and (dr.ndim != 2 or dr.shape != (V, 2)):
+        raise RuntimeError("infer_scan: depth_ranges must be [V,2] (depth_min, depth_max) with depth_range_kind = 'min_max', "
+                           "got %s for %d views" % (dr.shape, V))
     if dr.ndim != 2 or dr.shape[0] != V or dr.shape[1] < 2:
         raise RuntimeError("infer_scan: depth_ranges must be [V,2] (depth_min, depth_interval) or depth_values [V,ndv], "
                            "got %s for %d views" % (dr.shape, V))
@@ -77,7 +92,9 @@ def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192):
             srcs = srcs + [srcs[0]] * (nviews - len(srcs))                  # general_eval4.py:47-49
         ref_views.append(r)
         table.append([r] + srcs[:nviews - 1])
-        if dr.shape[1] == 2:
+        if depth_range_kind == "min_max":
+            dvs.append(dr[r])                                               # np.array([depth_min, depth_max], float32)
+        elif dr.shape[1] == 2:
             # (the Python floats read_cam_file returns; a float32 array holds them exactly when they came from one)
             dvs.append(formats.depth_value_range(float(depth_ranges[r][0]), float(depth_ranges[r][1]), ndepths))
         else:
@@ -147,12 +164,89 @@ def _scaled_inputs(kind, H, W, Ks, max_h, max_w):
     return Hd, Wd, formats.scale_intrinsics(Ks, scale_h, scale_w)
 
 
+def _check_views(images):
+    """The images of a scan in the ``crop_rows`` / ``img_wh`` modes -> (kind, list of per-view arrays or tensors as given, V,
+    [(Hs, Ws)] per view): uint8 [H,W,3] views, whose sizes may differ, or float32 [3,H,W] ones."""
+    views = list(images)
+    if not views:
+        raise RuntimeError("infer_scan: no images")
+    for i, im in enumerate(views):
+        if not torch.is_tensor(im) and not isinstance(im, np.ndarray):
+            raise RuntimeError("infer_scan: image %d is a %s, not an array or a tensor" % (i, type(im).__name__))
+    dt = views[0].dtype
+    if any(im.dtype != dt for im in views):
+        raise RuntimeError("infer_scan: the images of a scan must have one dtype")
+    if dt in (torch.uint8, np.dtype(np.uint8)):
+        kind, sizes = "u8", [tuple(im.shape[:2]) for im in views]
+        bad = [i for i, im in enumerate(views) if im.ndim != 3 or im.shape[2] != 3]
+    elif dt in (torch.float32, np.dtype(np.float32)):
+        kind, sizes = "f32", [tuple(im.shape[1:]) for im in views]
+        bad = [i for i, im in enumerate(views) if im.ndim != 3 or im.shape[0] != 3]
+    else:
+        raise RuntimeError("infer_scan: images must be uint8 [V,H,W,3] or float32 [V,3,H,W], got %s" % (dt,))
+    if bad:
+        raise RuntimeError("infer_scan: image %d is %s: views must be uint8 [H,W,3] or float32 [3,H,W]"
+                           % (bad[0], tuple(views[bad[0]].shape)))
+    return kind, views, len(views), [(int(h), int(w)) for h, w in sizes]
+
+
+def _dataset_inputs(kind, sizes, Ks, crop_rows, img_wh):
+    """Target size, crop and intrinsics of the two dataset modes -> (Hd, Wd, (top, bottom, left, right), adjusted copy of
+    ``Ks``).  ``Ks`` comes and goes in the quarter-resolution convention; the loaders' own operations (``cy - top``,
+    datasets/tanks.py:58; a Python-float factor per view and axis, datasets/eth3d.py:89-90) act on the full-resolution
+    matrix in between -- the factors 4 and 1/4 are exact, so these are the loaders' bits."""
+    Ks = np.array(Ks, dtype=np.float32)
+    Ks[:, :2, :] *= 4.0
+    if crop_rows is not None:
+        top, bottom = int(crop_rows[0]), int(crop_rows[1])
+        if top < 0 or bottom < 0:
+            raise RuntimeError("infer_scan: crop_rows = %s" % ((top, bottom),))
+        for i, hw in enumerate(sizes):
+            if hw != sizes[0]:
+                raise RuntimeError("infer_scan: image %d is %dx%d but image 0 is %dx%d: with crop_rows all views of a scan must "
+                                   "have one size (nothing is resampled)" % ((i,) + hw + sizes[0]))
+        Hd, Wd = sizes[0][0] - top - bottom, sizes[0][1]
+        if Hd < 64 or Wd < 64 or Hd % 64 or Wd % 64:
+            raise RuntimeError("infer_scan: image size %dx%d with crop_rows = %s leaves %dx%d: H and W must be positive "
+                               "multiples of 64" % (sizes[0] + ((top, bottom), Hd, Wd)))
+        crop = (top, bottom, 0, 0)
+        Ks = formats.crop_intrinsics(Ks, top, 0)
+    else:
+        Wd, Hd = int(img_wh[0]), int(img_wh[1])
+        if Hd < 64 or Wd < 64 or Hd % 64 or Wd % 64:
+            raise RuntimeError("infer_scan: img_wh = (%d, %d): W and H must be positive multiples of 64" % (Wd, Hd))
+        for i, (h, w) in enumerate(sizes):
+            if h < Hd or w < Wd:
+                raise RuntimeError("infer_scan: image %d is %dx%d, smaller than img_wh = (%d, %d) (%dx%d): nothing here "
+                                   "enlarges an image" % (i, h, w, Wd, Hd, Hd, Wd))
+            Ks[i] = formats.scale_intrinsics(Ks[i], Hd / h, Wd / w)
+        crop = (0, 0, 0, 0)
+    if kind == "f32" and (any(hw != (Hd, Wd) for hw in sizes) or any(crop)):
+        raise RuntimeError("infer_scan: float32 images of %dx%d would be cropped or resampled to %dx%d, which is done for "
+                           "uint8 images only: pass the decoded 8-bit images as uint8 [H,W,3]" % (sizes[0] + (Hd, Wd)))
+    Ks[:, :2, :] /= 4.0
+    return Hd, Wd, crop, Ks
+
+
+def _check_source_counts(pairs, nviews, view_ids=None):
+    """The dataset modes cut a source list to ``nviews - 1`` and never pad it (datasets/tanks.py:68): a shorter list is
+    refused here, naming the view."""
+    for r, srcs in pairs:
+        if 0 < len(srcs) < nviews - 1:
+            name = int(r) if view_ids is None else int(view_ids[int(r)])
+            raise RuntimeError("infer_scan: reference view %d has %d source views, fewer than nviews - 1 = %d: the Tanks and "
+                               "Temples / ETH3D loaders would run it with %d views, but a captured graph has one view count, "
+                               "and padding the list (as the DTU loader does) would change the result; lower nviews or drop "
+                               "the view from pairs" % (name, len(srcs), nviews - 1, len(srcs) + 1))
+
+
 class ScanResult(dict):
     """What ``infer_scan`` returns: ``ref_views`` [R] (view numbers, host), ``depth`` and ``photometric_confidence`` [R,H,W]
     on the GPU, ``Ks`` [V,3,3] / ``Es`` [V,4,4] at output resolution (the stage-4 camera ``write_cam`` gets in the
     reference), ``pairs`` (reference views with sources, full source lists: what fusion reads), ``view_ids`` (file
-    numbers of the views), ``stats`` (``fpn_runs``, ``replays``, ``captured``) and whatever else ``keep`` named.  With ``max_h`` / ``max_w``:
-    ``images``, the resized uint8 images [V,H,W,3] on the GPU, and ``Ks`` from the scaled intrinsics."""
+    numbers of the views), ``stats`` (``fpn_runs``, ``replays``, ``captured``) and whatever else ``keep`` named.  With ``max_h`` / ``max_w``,
+    ``crop_rows`` or ``img_wh``: ``images``, the prepared uint8 images [V,H,W,3] on the GPU, and ``Ks`` from the adjusted
+    intrinsics."""
 
     def timings(self):
         """Milliseconds per phase (HIP events recorded by ``infer_scan``; synchronises)."""
@@ -271,7 +365,7 @@ def _run_fpn(model, runner, kind, dev_images, chunk, packed=None):
 @torch.no_grad()
 def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2,
                keep=("depth", "photometric_confidence"), ndepths=192, fpn_chunk=None, max_store_bytes=None, view_ids=None,
-               max_h=None, max_w=None):
+               max_h=None, max_w=None, crop_rows=None, img_wh=None, depth_range_kind="min_interval"):
     """Depth and confidence maps of all reference views of a scan.
 
     ``images``: uint8 [V,H,W,3] (NumPy, or a tensor on the GPU) or float32 [V,3,H,W] in 0..1, or a sequence of per-view
@@ -294,27 +388,60 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     result's ``images`` are the resized uint8 images on the GPU (``write_scan_outputs`` and ``reconstruct_scan`` take
     them).  The source stack is extra device memory until the FPN has run -- ``V * Hs * Ws * 3`` bytes, 282 MB for 49
     views of 1200 x 1600 -- and counts towards ``max_store_bytes``.  float32 images that would need resampling and views
-    of different native sizes raise.  -> ScanResult."""
+    of different native sizes raise.
+
+    The reference's two other evaluation loaders (each alone, and not together with ``max_h`` / ``max_w``), both usually
+    with ``depth_range_kind="min_max"`` (``plan_scan``: ``depth_ranges`` [V,2] = (depth_min, depth_max) per view, passed to
+    the forward as they are):
+
+    * ``crop_rows=(top, bottom)``, ``(28, 28)`` for Tanks and Temples (``datasets/tanks.py:53-60``): these rows are cut off
+      every view without resampling and ``cy`` is shifted by ``top``.  All views must have one size and what is left must
+      be admissible.
+    * ``img_wh=(W, H)``, ``(1920, 1280)`` for ETH3D (``datasets/eth3d.py:57-62, :89-90``): every view is resized to this
+      size, its intrinsics scaled by its own ``W / Ws``, ``H / Hs``.  ``images`` may be a sequence of views of different
+      native sizes; none may be smaller than the target.
+
+    Both run in ``ops.load_pack_images_u8``, one launch for the scan; the result carries ``images`` (the prepared uint8
+    images on the GPU) and the adjusted ``Ks``, and the source bytes count towards ``max_store_bytes``, as above.  These
+    loaders cut a source list to ``nviews - 1`` and never pad it: a reference view with fewer sources raises, naming the
+    view (a captured graph has one view count, and padding would change the result).  -> ScanResult."""
     scaling = max_h is not None or max_w is not None
-    kind, images, V, H, W = _check_images(images, scaling)
+    prepare = crop_rows is not None or img_wh is not None
+    if prepare and (scaling or (crop_rows is not None and img_wh is not None)):
+        raise RuntimeError("infer_scan: crop_rows, img_wh and max_h / max_w are three loaders' image preparations: give one "
+                           "of them")
+    if prepare:
+        stack = images if torch.is_tensor(images) and images.dim() == 4 else None
+        kind, images, V, sizes = _check_views(images)
+    else:
+        kind, images, V, H, W = _check_images(images, scaling)
     if len(Ks) != V or len(Es) != V:
         raise RuntimeError("infer_scan: %d images for %d intrinsics and %d extrinsics" % (V, len(Ks), len(Es)))
-    Hs, Ws = H, W
+    crop = None
+    if prepare:
+        H, W, crop, Ks = _dataset_inputs(kind, sizes, Ks, crop_rows, img_wh)
+        Hs, Ws = sizes[0]
+        _check_source_counts(_as_pairs(pairs, V), nviews, view_ids)
+        if kind == "f32":                                                   # (already at the target size: nothing to prepare)
+            images = torch.stack(images) if torch.is_tensor(images[0]) else np.stack(images)
+    else:
+        Hs, Ws = H, W
     if scaling:
         H, W, Ks = _scaled_inputs(kind, Hs, Ws, Ks, max_h, max_w)
-    resize = scaling and kind == "u8"
-    plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths)
+    resize = (scaling or prepare) and kind == "u8"
+    plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths, depth_range_kind)
     if in_flight < 1:
         raise RuntimeError("infer_scan: in_flight = %d" % in_flight)
     chunk = int(fpn_chunk or nviews)
     if not 1 <= chunk <= 16:
         raise RuntimeError("infer_scan: fpn_chunk = %d (1..16 images per FPN run)" % chunk)
     need = store_bytes(V, H, W, model.feature.out_channels[-1])
-    source_bytes = V * Hs * Ws * 3 if resize else 0
+    source_bytes = (sum(h * w * 3 for h, w in sizes) if prepare else V * Hs * Ws * 3) if resize else 0
     if max_store_bytes is not None and resize and need + source_bytes > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d and the %dx%d source images need %d + %d bytes "
                            "(%.2f GB), more than max_store_bytes = %d"
-                           % (V, H, W, Hs, Ws, need, source_bytes, (need + source_bytes) / 1e9, max_store_bytes))
+                           % (V, H, W, max(h for h, _ in sizes) if prepare else Hs, max(w for _, w in sizes) if prepare else Ws,
+                              need, source_bytes, (need + source_bytes) / 1e9, max_store_bytes))
     if max_store_bytes is not None and need > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d need %d bytes (%.2f GB), more than "
                            "max_store_bytes = %d" % (V, H, W, need, need / 1e9, max_store_bytes))
@@ -332,7 +459,9 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
 
     with torch.cuda.device(dev):
         ev["upload"][0].record(main)
-        if torch.is_tensor(images):
+        if crop is not None and kind == "u8":
+            dev_images = None                                                # (ops.load_pack_images_u8 uploads the views itself)
+        elif torch.is_tensor(images):
             dev_images = images.to(dev).contiguous()
         else:
             dev_images = torch.from_numpy(np.ascontiguousarray(images)).to(dev)
@@ -342,7 +471,10 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
 
         ev["fpn"][0].record(main)
         packed = small = None
-        if resize:
+        if resize and crop is not None:
+            packed, small = ops.load_pack_images_u8(images if stack is None else stack, H, W, crop=crop, want_u8=True,
+                                                    device=dev)
+        elif resize:
             packed, small = ops.resize_pack_images_u8(dev_images, H, W, want_u8=True)
         fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk, packed)
         del dev_images, packed                                               # (the source stack goes back to the allocator)
@@ -411,20 +543,31 @@ def _pick(outputs, name):
     return cur
 
 
-def read_scan_folder(datapath, scan, interval_scale=1.06, ndepths=192):
+DATASETS = {"general": ("cams", None), "tanks": ("cams", None), "eth3d": ("cams_1", 1)}   # cam folder, negative depth_min -> ...
+
+
+def read_scan_folder(datapath, scan, interval_scale=1.06, ndepths=192, dataset="general"):
     """``datapath/scan/{images_post|images}/%08d.jpg``, ``cams/%08d_cam.txt``, ``pair.txt`` -> dict with ``images`` (list of
     uint8 [H,W,3]), ``Ks``, ``Es``, ``depth_ranges``, ``pairs`` (indices into the views) and ``view_ids`` (their file
-    numbers, sorted): everything ``infer_scan`` takes.  Every file is read once."""
+    numbers, sorted): everything ``infer_scan`` takes.  Every file is read once.
+
+    ``dataset="tanks"`` / ``"eth3d"``: the layouts ``datasets/tanks.py`` (``images/``, ``cams/``) and ``datasets/eth3d.py``
+    (``images/``, ``cams_1/``) read, through ``formats.read_cam_file_minmax`` (ETH3D: a negative depth_min becomes 1):
+    ``depth_ranges`` holds (depth_min, depth_max) -- ``depth_range_kind="min_max"`` -- and ``Ks`` the files' intrinsics
+    brought to the quarter-resolution convention ``infer_scan`` takes (rows 0-1 divided by 4, exact)."""
     from PIL import Image
+    if dataset not in DATASETS:
+        raise RuntimeError("infer_scan_folder: dataset = %r (one of %s)" % (dataset, ", ".join(sorted(DATASETS))))
+    cams, negative_min_to = DATASETS[dataset]
     root = os.path.join(datapath, scan)
     file_pairs = formats.read_pair_file(os.path.join(root, "pair.txt"))
     view_ids = sorted({v for r, srcs in file_pairs for v in [r] + srcs})
     paths = {}
     for v in view_ids:
         img = os.path.join(root, "images_post", "{:0>8}.jpg".format(v))
-        if not os.path.exists(img):
+        if dataset != "general" or not os.path.exists(img):
             img = os.path.join(root, "images", "{:0>8}.jpg".format(v))
-        cam = os.path.join(root, "cams", "{:0>8}_cam.txt".format(v))
+        cam = os.path.join(root, cams, "{:0>8}_cam.txt".format(v))
         for f in (img, cam):
             if not os.path.exists(f):
                 raise RuntimeError("infer_scan_folder: pair.txt names view %d, but %s does not exist" % (v, f))
@@ -433,7 +576,11 @@ def read_scan_folder(datapath, scan, interval_scale=1.06, ndepths=192):
     images, Ks, Es, ranges = [], [], [], []
     for v in view_ids:
         images.append(np.array(Image.open(paths[v][0]), dtype=np.uint8))
-        K, E, dmin, dint = formats.read_cam_file(paths[v][1], interval_scale, ndepths)
+        if dataset == "general":
+            K, E, dmin, dint = formats.read_cam_file(paths[v][1], interval_scale, ndepths)
+        else:
+            K, E, dmin, dint = formats.read_cam_file_minmax(paths[v][1], negative_min_to)   # (dint: depth_max here)
+            K[:2, :] /= 4.0
         Ks.append(K)
         Es.append(E)
         ranges.append((dmin, dint))
@@ -441,21 +588,52 @@ def read_scan_folder(datapath, scan, interval_scale=1.06, ndepths=192):
                 pairs=[(slot[r], [slot[v] for v in srcs]) for r, srcs in file_pairs])
 
 
-def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, max_h=None, max_w=None):
+def _dataset_keywords(dataset, kw):
+    """The keywords ``dataset`` stands for, unless the caller gave them: Tanks ``crop_rows=(28, 28)``, ETH3D
+    ``img_wh=(1920, 1280)`` (the loaders' own constants), both ``depth_range_kind="min_max"``."""
+    kw = dict(kw)
+    if dataset == "tanks" and kw.get("crop_rows") is None and kw.get("img_wh") is None:
+        kw["crop_rows"] = (28, 28)
+    if dataset == "eth3d" and kw.get("crop_rows") is None and kw.get("img_wh") is None:
+        kw["img_wh"] = (1920, 1280)
+    if dataset != "general":
+        kw.setdefault("depth_range_kind", "min_max")
+    return kw
+
+
+def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, max_h=None, max_w=None, dataset="general",
+                     crop_rows=None, img_wh=None, depth_range_kind=None):
     """Host planning of ``infer_scan_folder`` -> (the ``read_scan_folder`` dict, ScanPlan); no device work.  With ``max_h`` /
-    ``max_w`` the plan is made from the scaled intrinsics (the dict keeps the files' own)."""
-    sc = read_scan_folder(datapath, scan, interval_scale, ndepths)
+    ``max_w``, ``crop_rows`` or ``img_wh`` the plan is made from the adjusted intrinsics (the dict keeps the files' own)."""
+    sc = read_scan_folder(datapath, scan, interval_scale, ndepths, dataset)
+    kw = _dataset_keywords(dataset, dict(crop_rows=crop_rows, img_wh=img_wh, **({} if depth_range_kind is None else
+                                                                                {"depth_range_kind": depth_range_kind})))
+    crop_rows, img_wh, kind_dr = kw["crop_rows"], kw["img_wh"], kw.get("depth_range_kind", "min_interval")
     scaling = max_h is not None or max_w is not None
-    kind, _, _, H, W = _check_images(sc["images"], scaling)
-    Ks = _scaled_inputs(kind, H, W, sc["Ks"], max_h, max_w)[2] if scaling else sc["Ks"]
-    return sc, plan_scan(Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths)
+    if crop_rows is not None or img_wh is not None:
+        if scaling or (crop_rows is not None and img_wh is not None):
+            raise RuntimeError("infer_scan: crop_rows, img_wh and max_h / max_w are three loaders' image preparations: give "
+                               "one of them")
+        kind, _, V, sizes = _check_views(sc["images"])
+        Ks = _dataset_inputs(kind, sizes, sc["Ks"], crop_rows, img_wh)[3]
+        _check_source_counts(_as_pairs(sc["pairs"], V), nviews, sc["view_ids"])
+    else:
+        kind, _, _, H, W = _check_images(sc["images"], scaling)
+        Ks = _scaled_inputs(kind, H, W, sc["Ks"], max_h, max_w)[2] if scaling else sc["Ks"]
+    return sc, plan_scan(Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths, kind_dr)
 
 
-def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, **kw):
+def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, dataset="general", **kw):
     """``infer_scan`` on a scan folder in the reference's layout (``general_eval4.MVSDataset``).  The result's
     ``ref_views`` / ``pairs`` index ``view_ids`` (the file numbers).  ``max_h`` / ``max_w`` (the loader's arguments) go
-    through to ``infer_scan``: a scan is taken at its native image size, as the dataset ships it."""
-    sc = read_scan_folder(datapath, scan, interval_scale, ndepths)
+    through to ``infer_scan``: a scan is taken at its native image size, as the dataset ships it.
+
+    ``dataset="tanks"``: a Tanks and Temples scan folder (``datapath`` includes the split) as ``datasets/tanks.py`` takes it --
+    ``crop_rows=(28, 28)`` and ``depth_range_kind="min_max"`` unless given; the loader's default of 7 views is the caller's
+    ``nviews=7``.  ``dataset="eth3d"``: ``datasets/eth3d.py`` -- ``cams_1/``, ``img_wh=(1920, 1280)`` unless given,
+    ``depth_range_kind="min_max"``."""
+    sc = read_scan_folder(datapath, scan, interval_scale, ndepths, dataset)
+    kw = _dataset_keywords(dataset, kw)
     res = infer_scan(model, sc["images"], sc["Ks"], sc["Es"], sc["depth_ranges"], sc["pairs"], nviews=nviews,
                      ndepths=ndepths, view_ids=sc["view_ids"], **kw)
     res.setdefault("images", sc["images"])                                  # (the resized ones where infer_scan scaled)
@@ -513,14 +691,19 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
 
     Every source view a reference view's pair lists must have a depth map of its own, i.e. be a reference view with
     sources itself (the reference's ``filter_depth`` reads its ``depth_est`` file).  Colours come from the INPUT images
-    (with ``max_h`` / ``max_w``: from the resized ones, the pixels the reference writes to ``images/``), not from the
+    (with ``max_h`` / ``max_w``, ``crop_rows`` or ``img_wh``: from the prepared ones, the pixels the reference writes to
+    ``images/``), not from the
     re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same, colours differ
     by the JPEG re-encoding the reference adds."""
     from . import fusion
-    kind, images, V, H, W = _check_images(images, kw.get("max_h") is not None or kw.get("max_w") is not None)
+    prepare = kw.get("crop_rows") is not None or kw.get("img_wh") is not None
+    if not prepare:                                                          # (these modes take views of different sizes)
+        kind, images, V, H, W = _check_images(images, kw.get("max_h") is not None or kw.get("max_w") is not None)
     scan = infer_scan(model, images, Ks, Es, depth_ranges, pairs, **kw)
     if torch.is_tensor(scan.get("images")):
         kind, images = "u8", scan["images"]                                  # uint8 [V,Hd,Wd,3], already on the device
+    elif prepare:
+        kind, images, V, H, W = _check_images(images)                        # (float32 views already at the target size)
     slot = {int(r): i for i, r in enumerate(scan["ref_views"])}
     fpairs = []
     for r, srcs in scan["pairs"]:
