@@ -43,34 +43,25 @@ int mvster_pack_images(const float* const* imgs, int N, float* out, int B, int H
  * one launch and from a quarter of the bytes. */
 int mvster_pack_images_u8(const unsigned char* imgs, float* out, int V, int H, int W, void* stream);
 
-/* mvster_pack_images_u8 with the evaluation loader's input scaling in the same pass (datasets/general_eval4.py:92-109:
- * cv2.resize with default arguments -- bilinear, on read_img's floats): imgs uint8 [V,Hs,Ws,3] (4-byte aligned) ->
+/* mvster_pack_images_u8 with the image preparation of the reference's three evaluation loaders in the same pass, for a whole
+ * scan in one launch: the input scaling of datasets/general_eval4.py:92-109 (cv2.resize with default arguments -- bilinear,
+ * on read_img's floats), a crop (datasets/tanks.py:53-60) and a resize of every view from its own native size to one target
+ * (datasets/eth3d.py:57-62).  buf: one ragged byte buffer (16-byte aligned, buf_bytes long) holding the decoded uint8
+ * [Hs_v,Ws_v,3] images.  desc: V descriptors of 12 32-bit words each, on the DEVICE; desc_host: the same bytes on the HOST,
+ * which is what is validated before the launch.  Words: [0],[1] byte offset of the image in buf (low, high; a multiple of
+ * 16), [2] Hs, [3] Ws, [4] y0, [5] x0, [6] hw, [7] ww = the source window (the crop), [8] word offset into `tables` of that
+ * window size's tap tables (a multiple of 4), [9] area flag: non-zero exactly where ww == 2 Wd and hw == 2 Hd (per view),
+ * [10],[11] zero.  tables: table_words 32-bit words (16-byte aligned; may be NULL with table_words == 0).  One tap table is
+ * 2 Wd + 2 Hd words -- first tap sx [Wd] (int32), fraction fx [Wd] (float32), then sy [Hd], fy [Hd] -- built on the host
+ * for hw x ww -> Hd x Wd as OpenCV builds xofs / alpha (mvster_amd.formats.resize_tables), tap indices relative to the
+ * window; arithmetic in csrc/resize_math.h.  Where the area flag is set, the 2 x 2 mean of OpenCV's area path.
  * out [V,1,Hd,Wd,4] float RGB0 and, where out_u8 is not NULL, out_u8 [V,Hd,Wd,3] = trunc(clip(x * 255, 0, 255)), the pixels
- * test_mvs4.py:262-264 writes to images/.  tables: 2 Wd + 2 Hd 32-bit words (16-byte aligned) -- first tap sx [Wd] (int32),
- * fraction fx [Wd] (float32), then sy [Hd], fy [Hd] -- built on the host as OpenCV builds xofs / alpha
- * (mvster_amd.formats.resize_tables); arithmetic in csrc/resize_math.h.  At Ws == 2 Wd and Hs == 2 Hd the 2 x 2 mean of
- * OpenCV's area path.  Hs == Hd and Ws == Wd gives the bits of mvster_pack_images_u8.  The loader never enlarges:
- * Hd > Hs or Wd > Ws, like Hd / Wd that are not positive multiples of 64, is MVSTER_ERR_SHAPE.  The tables are trusted
- * for the values, not for the addresses: tap indices are clamped into the image. */
-int mvster_resize_pack_images_u8(const unsigned char* imgs, const void* tables, float* out, unsigned char* out_u8, int V, int Hs,
-                                 int Ws, int Hd, int Wd, void* stream);
-
-/* mvster_resize_pack_images_u8 with per-view addressing: the image preparation of the reference's two other evaluation
- * loaders for a whole scan in one launch -- a crop (datasets/tanks.py:53-60) and a resize of every view from its own native
- * size to one target (datasets/eth3d.py:57-62).  buf: one ragged byte buffer (16-byte aligned, buf_bytes long) holding the
- * decoded uint8 [Hs_v,Ws_v,3] images.  desc: V descriptors of 12 32-bit words each, on the DEVICE; desc_host: the same bytes
- * on the HOST, which is what is validated before the launch.  Words: [0],[1] byte offset of the image in buf (low, high;
- * a multiple of 16), [2] Hs, [3] Ws, [4] y0, [5] x0, [6] hw, [7] ww = the source window (the crop), [8] word offset into
- * `tables` of that window size's tap tables (2 Wd + 2 Hd words laid out as for mvster_resize_pack_images_u8, built for
- * hw x ww -> Hd x Wd, tap indices relative to the window; a multiple of 4), [9] area flag: non-zero exactly where
- * ww == 2 Wd and hw == 2 Hd (per view), [10],[11] zero.  tables: table_words 32-bit words (16-byte aligned; may be NULL with
- * table_words == 0).  out [V,1,Hd,Wd,4] float RGB0 and, where out_u8 is not NULL, out_u8 [V,Hd,Wd,3], both exactly as
- * mvster_resize_pack_images_u8 writes them: with equal descriptors and full-image windows the two entries agree bit for bit.
- * A window of hw == Hd and ww == Wd reads no table and gives the bits of mvster_pack_images_u8 on the cropped image, whatever
- * the alignment of its first byte and of the row pitch 3 Ws.  No path enlarges: Hd > hw or Wd > ww is MVSTER_ERR_SHAPE, as
- * are Hd / Wd that are not positive multiples of 64, an image that does not lie inside buf, a window that does not lie
- * inside its image, a table range outside `tables`, an area flag that does not match the sizes, and V > 65535.  Tap indices
- * are clamped into the window. */
+ * test_mvs4.py:262-264 writes to images/.  A window of hw == Hd and ww == Wd reads no table and gives the bits of
+ * mvster_pack_images_u8 on the cropped image, whatever the alignment of its first byte and of the row pitch 3 Ws.  No path
+ * enlarges: Hd > hw or Wd > ww is MVSTER_ERR_SHAPE, as are Hd / Wd that are not positive multiples of 64, an image that does
+ * not lie inside buf, a window that does not lie inside its image, a table range outside `tables`, an area flag that does
+ * not match the sizes, and V > 65535.  The tables are trusted for the values, not for the addresses: tap indices are
+ * clamped into the window. */
 int mvster_load_pack_images_u8(const unsigned char* buf, long buf_bytes, const int* desc_host, const int* desc, const void* tables,
                                long table_words, float* out, unsigned char* out_u8, int V, int Hd, int Wd, void* stream);
 

@@ -22,7 +22,6 @@ SIGNATURES = {
     "mvster_relative_projection_multi": [_f, _i, _f, _i, _i, _f],
     "mvster_pack_images": [_f, _i, _f, _i, _i, _i, _f],
     "mvster_pack_images_u8": [_f, _f, _i, _i, _i, _f],
-    "mvster_resize_pack_images_u8": [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f],
     "mvster_load_pack_images_u8": [_f, _l, _f, _f, _f, _l, _f, _f, _i, _i, _i, _f],
     "mvster_forward_prologue": [_f, _i, _f, _i, _i, _i, _f, _i, _f, _f, _i, _f, _i, _i, _i, _i, _f],
     "mvster_warp_agg_fwd": [_f, _f, _f, _f, _f, _f] + [_i] * 9 + [_l] * 3 + [_i, _i, _fl, _i, _f],

@@ -1,6 +1,6 @@
 // Per-pixel arithmetic of the evaluation loader's input scaling (general_eval4.py:92-109): cv2.resize(img, (Wd, Hd)) with
 // default arguments (INTER_LINEAR) on the float32 image read_img returns, restated from OpenCV's resize.cpp (float path,
-// scalar form).  Shared by stage_ops.hip (resize_pack_images_u8_kernel) and a host build used only by the tests
+// scalar form).  Shared by stage_ops.hip (load_pack_images_u8_kernel) and a host build used only by the tests
 // (tests/hostmath/resize_hostmath.cpp).
 //
 // The per-axis tables (first tap sx / sy, fraction fx / fy) are built on the host (formats.resize_tables), as OpenCV builds

@@ -843,67 +843,26 @@ __global__ void __launch_bounds__(256) pack_images_u8_kernel(const unsigned char
     }
 }
 
-// The evaluation loader's input scaling (general_eval4.py:92-109: cv2.resize, INTER_LINEAR, on read_img's floats) fused into
-// the 8-bit pack: src uint8 [V,Hs,Ws,3] -> out [V,Hd,Wd,4] RGB0 float and, with U8, out_u8 [V,Hd,Wd,3] = trunc(clip(x * 255)).
-// Arithmetic: resize_math.h.  tab = the host-built per-axis tables as 32-bit words: sx [Wd] (int), fx [Wd] (float bits),
-// sy [Hd], fy [Hd].  A thread owns four consecutive output pixels of one row (Wd is a multiple of 64): four 16-byte stores
-// and three aligned dwords of 8-bit pixels; both passes in registers, four taps x three bytes per pixel.  Neighbouring
-// lanes read source bytes ~12 * Ws / Wd apart, so a wave's gathers fall into a handful of cache lines.  The tables come from
-// the caller; the tap indices are clamped into the image all the same, so that a bad table gives wrong pixels and never a
-// read outside the source stack.
-template <bool U8>
-__global__ void __launch_bounds__(256) resize_pack_images_u8_kernel(const unsigned char* __restrict__ src, const int* __restrict__ tab,
-                                                                    float* __restrict__ out, unsigned char* __restrict__ out_u8,
-                                                                    int Hs, int Ws, int Hd, int Wd, int area, unsigned groups) {
-    const unsigned q = blockIdx.x * 256u + threadIdx.x;              // group of four pixels
-    if (q >= groups) return;
-    const unsigned wq = (unsigned)Wd >> 2;
-    const unsigned row = q / wq, xq = q - row * wq;                  // row = v * Hd + y
-    const unsigned v = row / (unsigned)Hd, y = row - v * (unsigned)Hd;
-    const int y0 = mv::clampi(tab[2 * Wd + y], Hs - 1), y1 = rsz::tap1(y0, Hs);
-    const float fy = __int_as_float(tab[2 * Wd + Hd + y]);
-    const unsigned char* img = src + (long)v * Hs * Ws * 3;
-    const unsigned char* r0 = img + (long)y0 * Ws * 3;
-    const unsigned char* r1 = img + (long)y1 * Ws * 3;
-    const int4 sx4 = *reinterpret_cast<const int4*>(tab + xq * 4);
-    const int4 fx4 = *reinterpret_cast<const int4*>(tab + Wd + xq * 4);
-    const int sx[4] = {sx4.x, sx4.y, sx4.z, sx4.w}, fxb[4] = {fx4.x, fx4.y, fx4.z, fx4.w};
-    const mv::Recip k255 = mv::make_recip(255.0f);
-    const long p0 = (long)row * Wd + xq * 4;
-    unsigned char by[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x0 = mv::clampi(sx[k], Ws - 1);
-        float rgb[3];
-        rsz::pixel(r0, r1, x0, rsz::tap1(x0, Ws), __int_as_float(fxb[k]), fy, area != 0, k255, rgb);
-        st4(out + (p0 + k) * 4, (f32x4){rgb[0], rgb[1], rgb[2], 0.0f});
-        if (U8) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) by[3 * k + c] = rsz::to_u8(rgb[c]);
-        }
-    }
-    if (U8) {
-        unsigned* w = reinterpret_cast<unsigned*>(out_u8 + p0 * 3);  // 12 bytes per group: 4-byte aligned
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            w[j] = (unsigned)by[4 * j] | ((unsigned)by[4 * j + 1] << 8) | ((unsigned)by[4 * j + 2] << 16) | ((unsigned)by[4 * j + 3] << 24);
-    }
-}
-
-// The Tanks and Temples / ETH3D loaders' image preparation (datasets/tanks.py:53-60: a crop; datasets/eth3d.py:57-62: every
-// view resized to one img_wh from its OWN native size) fused into the 8-bit pack, for all views of a scan in one launch:
-// resize_pack_images_u8_kernel with per-view addressing.  buf = one ragged byte buffer of the decoded images; desc = per view
-// LOAD_PACK_DESC_WORDS 32-bit words (include/mvster_hip.h): byte offset of the image (low, high word), native Hs, Ws, the
-// source window y0, x0, hw, ww, the word offset of the window size's tap tables in `tabs` (laid out as for
-// resize_pack_images_u8_kernel, indices relative to the window), the area flag.  blockIdx.y is the view, so the descriptor is
-// uniform over the workgroup: it is read once through the scalar cache, not per lane.  Hd * Wd / 4 is a multiple of 1024
-// (both are multiples of 64), so blockIdx.x covers a view's groups of four pixels exactly.
+// The image preparation of the reference's three evaluation loaders fused into the 8-bit pack, for all views of a scan in one
+// launch: the input scaling of general_eval4.py:92-109 (cv2.resize, INTER_LINEAR, on read_img's floats), the crop of
+// datasets/tanks.py:53-60, the resize of every view to one img_wh from its OWN native size of datasets/eth3d.py:57-62.
+// buf = one ragged byte buffer of the decoded uint8 [Hs,Ws,3] images -> out [V,Hd,Wd,4] RGB0 float and, with U8, out_u8
+// [V,Hd,Wd,3] = trunc(clip(x * 255)).  desc = per view LOAD_PACK_DESC_WORDS 32-bit words (include/mvster_hip.h): byte offset
+// of the image (low, high word), native Hs, Ws, the source window y0, x0, hw, ww, the word offset of the window size's tap
+// tables in `tabs`, the area flag.  A table = the host-built per-axis taps as 32-bit words, indices relative to the window:
+// sx [Wd] (int), fx [Wd] (float bits), sy [Hd], fy [Hd].  blockIdx.y is the view, so the descriptor is uniform over the
+// workgroup: it is read once through the scalar cache, not per lane.  Hd * Wd / 4 is a multiple of 1024 (both are multiples
+// of 64), so blockIdx.x covers a view's groups of four pixels exactly.
+// A thread owns four consecutive output pixels of one row: four 16-byte stores and three aligned dwords of 8-bit pixels; both
+// passes in registers, four taps x three bytes per pixel.  Neighbouring lanes read source bytes ~12 * ww / Wd apart, so a
+// wave's gathers fall into a handful of cache lines.
 // A window that already has the output size (a pure crop; Tanks always) takes no taps: 12 source bytes per thread, as
 // pack_images_u8_kernel reads them.  Their address is 3 * ((y0 + y) * Ws + x0) + 12 * xq behind a 16-byte aligned image, so
 // it is 4-byte aligned for every lane only where the window's first byte and the row pitch 3 * Ws both are; a lane takes the
 // three dword loads where its own address is aligned and twelve byte loads otherwise -- the same bytes either way.
-// Arithmetic: resize_math.h, unchanged.  Tap indices are clamped into the window (a bad table: wrong pixels, no read
-// outside the window); the windows themselves are checked on the host before the launch.
+// Arithmetic: resize_math.h.  The tables come from the caller; the tap indices are clamped into the window all the same, so
+// that a bad table gives wrong pixels and never a read outside the window.  The windows themselves are checked on the host
+// before the launch.
 constexpr int LOAD_PACK_DESC_WORDS = 12;
 
 template <bool U8>
@@ -1277,24 +1236,6 @@ extern "C" int mvster_pack_images_u8(const unsigned char* imgs, float* out, int 
     const long n = (long)V * H * W, groups = (n + 3) / 4;
     if ((groups + 255) / 256 > 0x7fffffffL) return MVSTER_ERR_SHAPE;
     hipLaunchKernelGGL(pack_images_u8_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, imgs, out, n);
-    return mv_check_launch();
-}
-
-extern "C" int mvster_resize_pack_images_u8(const unsigned char* imgs, const void* tables, float* out, unsigned char* out_u8, int V,
-                                            int Hs, int Ws, int Hd, int Wd, void* stream) {
-    if (!imgs || !tables || !out) return MVSTER_ERR_NULL;
-    if (V <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0 || Hd % 64 || Wd % 64 || Hd > Hs || Wd > Ws) return MVSTER_ERR_SHAPE;
-    if (((uintptr_t)tables & 15) || ((uintptr_t)out_u8 & 3)) return MVSTER_ERR_SHAPE;
-    const long groups = (long)V * Hd * (Wd / 4);
-    if (groups > 0x7fffffffL) return MVSTER_ERR_SHAPE;
-    const int area = Ws == 2 * Wd && Hs == 2 * Hd;                   // OpenCV: INTER_LINEAR at exactly 2:1 on both axes is INTER_AREA
-    const dim3 grid((unsigned)((groups + 255) / 256));
-    if (out_u8)
-        hipLaunchKernelGGL(resize_pack_images_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, imgs, (const int*)tables, out,
-                           out_u8, Hs, Ws, Hd, Wd, area, (unsigned)groups);
-    else
-        hipLaunchKernelGGL(resize_pack_images_u8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, imgs, (const int*)tables, out,
-                           out_u8, Hs, Ws, Hd, Wd, area, (unsigned)groups);
     return mv_check_launch();
 }
 

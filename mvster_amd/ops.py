@@ -5,6 +5,8 @@ returns freshly allocated outputs.  Names and argument meaning follow the refere
 functions in models/mvs4net_utils.py; shapes at this level use the reference's layouts
 (NCHW / NCDHW) unless the name says ``_cl`` (channels-last).
 """
+import functools
+
 import torch
 
 from . import _lib
@@ -92,9 +94,8 @@ def resize_pack_images_u8(imgs_u8, Hd, Wd, want_u8=False):
     scaling (``cv2.resize`` with default arguments on ``read_img``'s floats; ``formats.resize_linear`` is the same
     arithmetic on the host) in the same launch, for all images of a scan.  ``want_u8``: also the resized images as uint8
     [V,Hd,Wd,3] = trunc(clip(x * 255, 0, 255)) -> (packed, u8).  ``Hd``, ``Wd``: multiples of 64, not larger than the
-    source.  The tap tables are built here (``formats.resize_tables``) and uploaded as one small buffer."""
-    import numpy as np
-    from . import formats
+    source.  The launch is ``load_pack_images_u8``'s, on full-image windows of one size: a stack whose views are a
+    multiple of 16 bytes long (every size the loaders produce) is read where it lies, any other one is copied once."""
     if not torch.is_tensor(imgs_u8) or not imgs_u8.is_cuda:
         raise RuntimeError("mvster_amd.ops.resize_pack_images_u8: expected a GPU tensor (the HIP path has no CPU fallback)")
     if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[3] != 3:
@@ -107,14 +108,7 @@ def resize_pack_images_u8(imgs_u8, Hd, Wd, want_u8=False):
     if Hd < 64 or Wd < 64 or Hd % 64 or Wd % 64 or Hd > Hs or Wd > Ws:
         raise RuntimeError("resize_pack_images_u8: target size %dx%d for %dx%d images: H and W must be positive multiples of 64 "
                            "and not larger than the source (the loader never enlarges)" % (Hd, Wd, Hs, Ws))
-    sx, fx, sy, fy = formats.resize_tables(Hs, Ws, Hd, Wd)
-    words = np.concatenate([sx.view(np.int32), fx.view(np.int32), sy.view(np.int32), fy.view(np.int32)])
-    tables = torch.from_numpy(words).to(x.device)
-    out = torch.empty(V, 1, Hd, Wd, 4, device=x.device, dtype=torch.float32)
-    u8 = torch.empty(V, Hd, Wd, 3, device=x.device, dtype=torch.uint8) if want_u8 else None
-    _lib.check(_lib.load().mvster_resize_pack_images_u8(_ptr(x), _ptr(tables), _ptr(out), _ptr(u8), V, Hs, Ws, Hd, Wd, _stream()),
-               "resize_pack_images_u8")
-    return (out, u8) if want_u8 else out
+    return load_pack_images_u8(x, Hd, Wd, want_u8=want_u8)
 
 
 LOAD_PACK_DESC_WORDS = 12      # per-view descriptor of mvster_load_pack_images_u8 (include/mvster_hip.h)
@@ -127,7 +121,14 @@ def load_pack_descriptors(sizes, Hd, Wd, crop=(0, 0, 0, 0)):
     window -> ``Hd`` x ``Wd``, built once per distinct window size and shared; a window that already has the output size has
     none), and the length in bytes of the ragged buffer (every view starts on a multiple of 16).  Raises where the kernel's
     entry point would return an error: ``Hd`` / ``Wd`` that are not positive multiples of 64, a crop that leaves nothing, a
-    window smaller than the output on either axis -- no path enlarges."""
+    window smaller than the output on either axis -- no path enlarges.  Memoised per argument set (the scans of a dataset
+    share one, and building it costs a good part of the launch it describes); every call gets arrays of its own."""
+    desc, tables, total = _load_pack_descriptors(tuple(map(tuple, sizes)), Hd, Wd, tuple(crop))
+    return desc.copy(), tables.copy(), total
+
+
+@functools.lru_cache(maxsize=16)
+def _load_pack_descriptors(sizes, Hd, Wd, crop):
     import numpy as np
     from . import formats
     Hd, Wd = int(Hd), int(Wd)
@@ -161,30 +162,34 @@ def load_pack_descriptors(sizes, Hd, Wd, crop=(0, 0, 0, 0)):
 
 
 def load_pack_images_u8(views, Hd, Wd, crop=(0, 0, 0, 0), want_u8=False, device=None):
-    """The image preparation of the reference's Tanks and Temples and ETH3D loaders for all views of a scan in one launch:
-    ``views`` = a sequence of uint8 [Hs_i,Ws_i,3] arrays or tensors (host or GPU; their native sizes may differ) ->
-    [V,1,Hd,Wd,4] channels-last RGB0 float32.  Each view is cropped by ``crop = (top, bottom, left, right)`` and the window
-    that remains resized to ``Hd`` x ``Wd`` with its own factors, in the arithmetic of ``resize_pack_images_u8`` (per view
+    """The image preparation of the reference's evaluation loaders for all views of a scan in one launch: ``views`` = a
+    sequence of uint8 [Hs_i,Ws_i,3] arrays or tensors (host or GPU; their native sizes may differ), or one stack
+    [V,Hs,Ws,3] -> [V,1,Hd,Wd,4] channels-last RGB0 float32.  Each view is cropped by ``crop = (top, bottom, left, right)``
+    and the window that remains resized to ``Hd`` x ``Wd`` with its own factors (per view
     ``formats.resize_linear(u8 / 255)`` of the window, bit for bit; the 2 x 2 mean where a window is exactly twice the output
     on both axes).  A window that already has the output size (``datasets/tanks.py``: 1080 rows minus 28 + 28) is only
-    converted: the bits of ``pack_images_u8`` on the slices.  ``want_u8``: also uint8 [V,Hd,Wd,3] as ``resize_pack_images_u8``
-    gives them -> (packed, u8).  **No path enlarges**: a window smaller than ``Hd`` x ``Wd`` on either axis raises, as do
-    ``Hd`` / ``Wd`` that are not positive multiples of 64.
+    converted: the bits of ``pack_images_u8`` on the slices.  ``want_u8``: also the prepared images as uint8 [V,Hd,Wd,3] =
+    trunc(clip(x * 255, 0, 255)) -> (packed, u8).  **No path enlarges**: a window smaller than ``Hd`` x ``Wd`` on either axis
+    raises, as do ``Hd`` / ``Wd`` that are not positive multiples of 64.
 
-    Host views go into one ragged buffer and up in ONE copy; descriptors and tap tables (``load_pack_descriptors``) in one more.
-    A contiguous GPU stack [V,Hs,Ws,3] whose views start on multiples of 16 bytes is read where it lies."""
+    A contiguous stack whose views are a multiple of 16 bytes long (the kernel's rule for where a view may start) is taken as
+    it lies: a host stack (``ndarray`` or CPU tensor) goes up in ONE copy of its flat view, a GPU stack is read in place.
+    Everything else -- a sequence of views, or a stack of e.g. 130 x 197 x 3 bytes per view -- is gathered into one ragged
+    buffer with every view on a multiple of 16 first: on the host, then ONE upload, or for GPU views with one device copy per
+    view.  Descriptors and tap tables (``load_pack_descriptors``) go up in one more copy."""
     import numpy as np
-    if torch.is_tensor(views) or isinstance(views, np.ndarray):
-        views = views if views.ndim == 4 else [views]
-    stack = views if torch.is_tensor(views) else None
-    views = list(views)
-    if not views:
+    one = torch.is_tensor(views) or isinstance(views, np.ndarray)
+    stack = views if one and views.ndim == 4 else None
+    # (the views of a stack share dtype and shape: the first stands for all of them until they have to be gathered)
+    views = list(stack[:1]) if stack is not None else [views] if one else list(views)
+    V = len(views) if stack is None else len(stack)
+    if not V:
         raise RuntimeError("load_pack_images_u8: no views")
     for i, im in enumerate(views):
         if im.dtype not in (torch.uint8, np.dtype(np.uint8)) or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
             raise RuntimeError("load_pack_images_u8: view %d: expects uint8 [H,W,3], got %s %s" % (i, im.dtype, tuple(im.shape)))
-    desc, tables, total = load_pack_descriptors([im.shape[:2] for im in views], Hd, Wd, crop)
-    V, Hd, Wd = len(views), int(Hd), int(Wd)
+    desc, tables, total = load_pack_descriptors([im.shape[:2] for im in views] * (V // len(views)), Hd, Wd, crop)
+    Hd, Wd = int(Hd), int(Wd)
     if V > 65535:
         raise RuntimeError("load_pack_images_u8: %d views (at most 65535 in one launch)" % V)
     if device is None:
@@ -193,22 +198,30 @@ def load_pack_images_u8(views, Hd, Wd, crop=(0, 0, 0, 0), want_u8=False, device=
     device = torch.device(device)
     if device.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("mvster_amd.ops.load_pack_images_u8 runs on the GPU only (the HIP path has no CPU fallback)")
-    offs = (desc[:, 0].astype(np.int64) & 0xffffffff) | (desc[:, 1].astype(np.int64) << 32)
-    per = views[0].shape[0] * views[0].shape[1] * 3
-    if (stack is not None and stack.is_cuda and stack.device == device and stack.is_contiguous() and per % 16 == 0
-            and stack.data_ptr() % 16 == 0):
-        buf = stack.reshape(-1)                                               # (equal sizes at a pitch of 16: the offsets hold)
-    elif any(torch.is_tensor(im) and im.is_cuda for im in views):
-        buf = torch.empty(total, dtype=torch.uint8, device=device)
-        for im, o in zip(views, offs):
-            im = im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))
-            buf[o:o + im.numel()].copy_(im.reshape(-1))
+    flat = None
+    if stack is not None and views[0].shape[0] * views[0].shape[1] * 3 % 16 == 0:   # (equal sizes at a pitch of 16: the offsets hold)
+        if torch.is_tensor(stack) and stack.is_contiguous():
+            flat = stack.reshape(-1)
+        elif isinstance(stack, np.ndarray) and stack.flags.c_contiguous:
+            flat = torch.from_numpy(stack.reshape(-1))
+    if flat is not None and not flat.is_cuda:
+        buf = flat.to(device)
+    elif flat is not None and flat.device == device and flat.data_ptr() % 16 == 0:
+        buf = flat
     else:
-        host = np.empty(total, dtype=np.uint8)
-        for im, o in zip(views, offs):
-            im = im.numpy() if torch.is_tensor(im) else im
-            host[o:o + im.size] = im.reshape(-1)
-        buf = torch.from_numpy(host).to(device)
+        views = views if stack is None else list(stack)
+        offs = (desc[:, 0].astype(np.int64) & 0xffffffff) | (desc[:, 1].astype(np.int64) << 32)
+        if any(torch.is_tensor(im) and im.is_cuda for im in views):
+            buf = torch.empty(total, dtype=torch.uint8, device=device)
+            for im, o in zip(views, offs):
+                im = im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))
+                buf[o:o + im.numel()].copy_(im.reshape(-1))
+        else:
+            host = np.empty(total, dtype=np.uint8)
+            for im, o in zip(views, offs):
+                im = im.numpy() if torch.is_tensor(im) else im
+                host[o:o + im.size] = im.reshape(-1)
+            buf = torch.from_numpy(host).to(device)
     # descriptors (V * 12 words: a multiple of 4, so the tables behind them stay 16-byte aligned) and tables: one upload
     blob_host = np.concatenate([desc.reshape(-1), tables])
     blob = torch.from_numpy(blob_host).to(device)

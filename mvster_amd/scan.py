@@ -20,12 +20,12 @@ Same kernels on the same operands as ``model(imgs, proj_matrices, depth_values)`
 
 Scans at their native image size (``max_h`` / ``max_w``): the loader's input scaling
 (``general_eval4.MVSDataset.scale_mvs_input``) runs in the launch that packs the 8-bit images
-(``ops.resize_pack_images_u8``), the intrinsics are scaled on the host.  Without these arguments all images of a scan
+(``ops.load_pack_images_u8``), the intrinsics are scaled on the host.  Without these arguments all images of a scan
 must have one admissible size.
 
 The reference's two other evaluation loaders (``crop_rows`` = ``datasets/tanks.py``, ``img_wh`` = ``datasets/eth3d.py``,
 ``depth_range_kind="min_max"`` for both): a crop, or a resize of every view from its own native
-size to one target, in the launch that packs the 8-bit images (``ops.load_pack_images_u8``).
+size to one target, in the same launch.  ``plan_inputs`` is the host side of all three.
 """
 import collections
 import os
@@ -113,8 +113,9 @@ def store_bytes(V, H, W, base_channels=8):
 
 
 def _check_images(images, scaling=False):
-    """-> ("u8", [V,H,W,3]) or ("f32", [V,3,H,W]) as given (array or tensor, not copied), after the shape checks.
-    ``scaling``: the caller brings the images to an admissible size (``_scaled_inputs``), so any one common size passes."""
+    """-> ("u8", [V,H,W,3], [(H, W)] * V) or ("f32", [V,3,H,W], ...): the stack as given (array or tensor, not copied; a
+    sequence of views is stacked), after the shape checks.  ``scaling``: the caller brings the images to an admissible size
+    (``_scaled_inputs``), so any one common size passes."""
     if not torch.is_tensor(images) and not isinstance(images, np.ndarray):
         images = list(images)
         if not images:
@@ -143,12 +144,10 @@ def _check_images(images, scaling=False):
         H, W = images.shape[2], images.shape[3]
     else:
         raise RuntimeError("infer_scan: images must be uint8 [V,H,W,3] or float32 [V,3,H,W], got %s" % (dt,))
-    if scaling and H > 0 and W > 0:
-        return kind, images, int(images.shape[0]), int(H), int(W)
-    if H % 64 or W % 64 or H == 0 or W == 0:
+    if (H % 64 or W % 64 or H == 0 or W == 0) and not (scaling and H > 0 and W > 0):
         raise RuntimeError("infer_scan: image size %dx%d: H and W must be multiples of 64 (resampling stays outside the "
                            "path: resize the images first)" % (H, W))
-    return kind, images, int(images.shape[0]), int(H), int(W)
+    return kind, images, [(int(H), int(W))] * int(images.shape[0])
 
 
 def _scaled_inputs(kind, H, W, Ks, max_h, max_w):
@@ -165,7 +164,7 @@ def _scaled_inputs(kind, H, W, Ks, max_h, max_w):
 
 
 def _check_views(images):
-    """The images of a scan in the ``crop_rows`` / ``img_wh`` modes -> (kind, list of per-view arrays or tensors as given, V,
+    """The images of a scan in the ``crop_rows`` / ``img_wh`` modes -> (kind, list of per-view arrays or tensors as given,
     [(Hs, Ws)] per view): uint8 [H,W,3] views, whose sizes may differ, or float32 [3,H,W] ones."""
     views = list(images)
     if not views:
@@ -187,7 +186,7 @@ def _check_views(images):
     if bad:
         raise RuntimeError("infer_scan: image %d is %s: views must be uint8 [H,W,3] or float32 [3,H,W]"
                            % (bad[0], tuple(views[bad[0]].shape)))
-    return kind, views, len(views), [(int(h), int(w)) for h, w in sizes]
+    return kind, views, [(int(h), int(w)) for h, w in sizes]
 
 
 def _dataset_inputs(kind, sizes, Ks, crop_rows, img_wh):
@@ -228,6 +227,46 @@ def _dataset_inputs(kind, sizes, Ks, crop_rows, img_wh):
     return Hd, Wd, crop, Ks
 
 
+ScanInputs = collections.namedtuple("ScanInputs", "kind images V sizes H W crop Ks source_bytes prepare exact_sources")
+ScanInputs.__doc__ = """What ``plan_inputs`` makes of a scan's images and intrinsics.  ``kind`` "u8" / "f32"; ``images`` as given
+(a stack, or the list of views; float32 views and, in the ``max_h`` / ``max_w`` mode, any sequence stacked); ``V``; ``sizes``
+[(Hs, Ws)] per view; the target ``H``, ``W``; ``crop`` (top, bottom, left, right); ``Ks`` adjusted to the prepared images;
+``prepare``: the images go through ``ops.load_pack_images_u8`` (uint8 images with one of the three preparations, even
+where it leaves the size alone), and ``source_bytes`` is what that reads; ``exact_sources``: the loader cuts source lists
+and never pads them (``_check_source_counts``)."""
+
+
+def plan_inputs(images, Ks, max_h=None, max_w=None, crop_rows=None, img_wh=None, Es=None):
+    """Host side of the three loaders' image preparations (pure NumPy, no device) -> ScanInputs.  ``max_h`` / ``max_w``:
+    every view resized to one target computed from the common native size, nothing cropped; ``crop_rows``, ``img_wh``:
+    ``_dataset_inputs``; none of them: the images must have one admissible size already.  ``Es``: where given, its length
+    and that of ``Ks`` are checked against the number of views."""
+    scaling = max_h is not None or max_w is not None
+    datasets = crop_rows is not None or img_wh is not None
+    if scaling + (crop_rows is not None) + (img_wh is not None) > 1:
+        raise RuntimeError("infer_scan: crop_rows, img_wh and max_h / max_w are three loaders' image preparations: give one "
+                           "of them")
+    if datasets:
+        kind, views, sizes = _check_views(images)
+        if not torch.is_tensor(images) and not isinstance(images, np.ndarray):
+            images = views                                                  # (a stack stays whole: it can be read where it lies)
+    else:
+        kind, images, sizes = _check_images(images, scaling)
+    V = len(sizes)
+    if Es is not None and (len(Ks) != V or len(Es) != V):
+        raise RuntimeError("infer_scan: %d images for %d intrinsics and %d extrinsics" % (V, len(Ks), len(Es)))
+    (H, W), crop = sizes[0], (0, 0, 0, 0)
+    if datasets:
+        H, W, crop, Ks = _dataset_inputs(kind, sizes, Ks, crop_rows, img_wh)
+        if kind == "f32" and images is views:                               # (already at the target size: nothing to prepare)
+            images = torch.stack(views) if torch.is_tensor(views[0]) else np.stack(views)
+    elif scaling:
+        H, W, Ks = _scaled_inputs(kind, H, W, Ks, max_h, max_w)
+    prepare = (scaling or datasets) and kind == "u8"
+    source_bytes = sum(h * w * 3 for h, w in sizes) if prepare else 0
+    return ScanInputs(kind, images, V, sizes, H, W, crop, Ks, source_bytes, prepare, datasets)
+
+
 def _check_source_counts(pairs, nviews, view_ids=None):
     """The dataset modes cut a source list to ``nviews - 1`` and never pad it (datasets/tanks.py:68): a shorter list is
     refused here, naming the view."""
@@ -249,7 +288,9 @@ class ScanResult(dict):
     intrinsics."""
 
     def timings(self):
-        """Milliseconds per phase (HIP events recorded by ``infer_scan``; synchronises)."""
+        """Milliseconds per phase (HIP events recorded by ``infer_scan``; synchronises).  ``upload``: the images and the
+        per-sample rows, and with ``max_h`` / ``max_w``, ``crop_rows`` or ``img_wh`` the launch that prepares and packs the
+        images (``ops.load_pack_images_u8``: the copy is the bulk of it) -- for all three, not under ``fpn``."""
         torch.cuda.synchronize()
         ev = self.get("events", {})
         return {k: a.elapsed_time(b) for k, (a, b) in ev.items()}
@@ -384,9 +425,9 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     ``max_h`` / ``max_w`` (both ``None``: nothing below applies): the reference loader's input scaling
     (``general_eval4.MVSDataset.scale_mvs_input``, e.g. 864 / 1152 for DTU).  uint8 images of any one common size are
     shrunk to fit, rounded down to multiples of 64 and resampled on the GPU in the launch that packs them
-    (``ops.resize_pack_images_u8``); ``Ks`` is scaled to match, and it is the scaled intrinsics the result carries.  The
+    (``ops.load_pack_images_u8``); ``Ks`` is scaled to match, and it is the scaled intrinsics the result carries.  The
     result's ``images`` are the resized uint8 images on the GPU (``write_scan_outputs`` and ``reconstruct_scan`` take
-    them).  The source stack is extra device memory until the FPN has run -- ``V * Hs * Ws * 3`` bytes, 282 MB for 49
+    them).  The source stack is extra device memory while it is packed -- ``V * Hs * Ws * 3`` bytes, 282 MB for 49
     views of 1200 x 1600 -- and counts towards ``max_store_bytes``.  float32 images that would need resampling and views
     of different native sizes raise.
 
@@ -401,34 +442,14 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
       size, its intrinsics scaled by its own ``W / Ws``, ``H / Hs``.  ``images`` may be a sequence of views of different
       native sizes; none may be smaller than the target.
 
-    Both run in ``ops.load_pack_images_u8``, one launch for the scan; the result carries ``images`` (the prepared uint8
-    images on the GPU) and the adjusted ``Ks``, and the source bytes count towards ``max_store_bytes``, as above.  These
-    loaders cut a source list to ``nviews - 1`` and never pad it: a reference view with fewer sources raises, naming the
-    view (a captured graph has one view count, and padding would change the result).  -> ScanResult."""
-    scaling = max_h is not None or max_w is not None
-    prepare = crop_rows is not None or img_wh is not None
-    if prepare and (scaling or (crop_rows is not None and img_wh is not None)):
-        raise RuntimeError("infer_scan: crop_rows, img_wh and max_h / max_w are three loaders' image preparations: give one "
-                           "of them")
-    if prepare:
-        stack = images if torch.is_tensor(images) and images.dim() == 4 else None
-        kind, images, V, sizes = _check_views(images)
-    else:
-        kind, images, V, H, W = _check_images(images, scaling)
-    if len(Ks) != V or len(Es) != V:
-        raise RuntimeError("infer_scan: %d images for %d intrinsics and %d extrinsics" % (V, len(Ks), len(Es)))
-    crop = None
-    if prepare:
-        H, W, crop, Ks = _dataset_inputs(kind, sizes, Ks, crop_rows, img_wh)
-        Hs, Ws = sizes[0]
+    Both run in the same launch; the result carries ``images`` (the prepared uint8 images on the GPU) and the adjusted
+    ``Ks``, and the source bytes count towards ``max_store_bytes``, as above.  These loaders cut a source list to
+    ``nviews - 1`` and never pad it: a reference view with fewer sources raises, naming the view (a captured graph has one
+    view count, and padding would change the result).  -> ScanResult."""
+    inp = plan_inputs(images, Ks, max_h, max_w, crop_rows, img_wh, Es)
+    kind, V, H, W, Ks = inp.kind, inp.V, inp.H, inp.W, inp.Ks
+    if inp.exact_sources:
         _check_source_counts(_as_pairs(pairs, V), nviews, view_ids)
-        if kind == "f32":                                                   # (already at the target size: nothing to prepare)
-            images = torch.stack(images) if torch.is_tensor(images[0]) else np.stack(images)
-    else:
-        Hs, Ws = H, W
-    if scaling:
-        H, W, Ks = _scaled_inputs(kind, Hs, Ws, Ks, max_h, max_w)
-    resize = (scaling or prepare) and kind == "u8"
     plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths, depth_range_kind)
     if in_flight < 1:
         raise RuntimeError("infer_scan: in_flight = %d" % in_flight)
@@ -436,12 +457,11 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     if not 1 <= chunk <= 16:
         raise RuntimeError("infer_scan: fpn_chunk = %d (1..16 images per FPN run)" % chunk)
     need = store_bytes(V, H, W, model.feature.out_channels[-1])
-    source_bytes = (sum(h * w * 3 for h, w in sizes) if prepare else V * Hs * Ws * 3) if resize else 0
-    if max_store_bytes is not None and resize and need + source_bytes > max_store_bytes:
+    if max_store_bytes is not None and inp.prepare and need + inp.source_bytes > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d and the %dx%d source images need %d + %d bytes "
                            "(%.2f GB), more than max_store_bytes = %d"
-                           % (V, H, W, max(h for h, _ in sizes) if prepare else Hs, max(w for _, w in sizes) if prepare else Ws,
-                              need, source_bytes, (need + source_bytes) / 1e9, max_store_bytes))
+                           % (V, H, W, max(h for h, _ in inp.sizes), max(w for _, w in inp.sizes), need, inp.source_bytes,
+                              (need + inp.source_bytes) / 1e9, max_store_bytes))
     if max_store_bytes is not None and need > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d need %d bytes (%.2f GB), more than "
                            "max_store_bytes = %d" % (V, H, W, need, need / 1e9, max_store_bytes))
@@ -459,25 +479,20 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
 
     with torch.cuda.device(dev):
         ev["upload"][0].record(main)
-        if crop is not None and kind == "u8":
-            dev_images = None                                                # (ops.load_pack_images_u8 uploads the views itself)
-        elif torch.is_tensor(images):
-            dev_images = images.to(dev).contiguous()
-        else:
-            dev_images = torch.from_numpy(np.ascontiguousarray(images)).to(dev)
         runner = _runner(model, V, H, W, nviews, plan.depth_values.shape[1])
+        packed = small = dev_images = None
+        if inp.prepare:                                                      # the upload and the launch that prepares and packs
+            packed, small = ops.load_pack_images_u8(inp.images, H, W, crop=inp.crop, want_u8=True, device=dev)
+        elif torch.is_tensor(inp.images):
+            dev_images = inp.images.to(dev).contiguous()
+        else:
+            dev_images = torch.from_numpy(np.ascontiguousarray(inp.images)).to(dev)
         samples = torch.from_numpy(runner.rows(plan, model.num_stage)).to(dev)   # all per-sample inputs: ONE upload
         ev["upload"][1].record(main)
 
         ev["fpn"][0].record(main)
-        packed = small = None
-        if resize and crop is not None:
-            packed, small = ops.load_pack_images_u8(images if stack is None else stack, H, W, crop=crop, want_u8=True,
-                                                    device=dev)
-        elif resize:
-            packed, small = ops.resize_pack_images_u8(dev_images, H, W, want_u8=True)
         fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk, packed)
-        del dev_images, packed                                               # (the source stack goes back to the allocator)
+        del dev_images, packed                                               # (the full-size stack goes back to the allocator)
         ev["fpn"][1].record(main)
 
         # [K,R,...] stacks of the kept maps; same-shaped ones share one allocation (one staging copy moves them all)
@@ -523,9 +538,9 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
                      Ks=k4[:, 1, :3, :3].copy(), Es=k4[:, 0].copy(),
                      view_ids=list(range(V)) if view_ids is None else [int(v) for v in view_ids],
                      stats={"fpn_runs": fpn_runs, "replays": R, "captured": captured_now, "store_bytes": need}, events=ev)
-    if resize:
+    if inp.prepare:
         res["images"] = small
-        res["stats"]["source_bytes"] = source_bytes
+        res["stats"]["source_bytes"] = inp.source_bytes
     for name, st in zip(keep, stacks):
         res[name] = st
     res.maps, res.map_names = maps, keep
@@ -609,18 +624,10 @@ def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192,
     kw = _dataset_keywords(dataset, dict(crop_rows=crop_rows, img_wh=img_wh, **({} if depth_range_kind is None else
                                                                                 {"depth_range_kind": depth_range_kind})))
     crop_rows, img_wh, kind_dr = kw["crop_rows"], kw["img_wh"], kw.get("depth_range_kind", "min_interval")
-    scaling = max_h is not None or max_w is not None
-    if crop_rows is not None or img_wh is not None:
-        if scaling or (crop_rows is not None and img_wh is not None):
-            raise RuntimeError("infer_scan: crop_rows, img_wh and max_h / max_w are three loaders' image preparations: give "
-                               "one of them")
-        kind, _, V, sizes = _check_views(sc["images"])
-        Ks = _dataset_inputs(kind, sizes, sc["Ks"], crop_rows, img_wh)[3]
-        _check_source_counts(_as_pairs(sc["pairs"], V), nviews, sc["view_ids"])
-    else:
-        kind, _, _, H, W = _check_images(sc["images"], scaling)
-        Ks = _scaled_inputs(kind, H, W, sc["Ks"], max_h, max_w)[2] if scaling else sc["Ks"]
-    return sc, plan_scan(Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths, kind_dr)
+    inp = plan_inputs(sc["images"], sc["Ks"], max_h, max_w, crop_rows, img_wh)
+    if inp.exact_sources:
+        _check_source_counts(_as_pairs(sc["pairs"], inp.V), nviews, sc["view_ids"])
+    return sc, plan_scan(inp.Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths, kind_dr)
 
 
 def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, dataset="general", **kw):
@@ -642,7 +649,7 @@ def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndep
 
 def _images_u8_hwc(images):
     """The scan's images as uint8 [V,H,W,3] on the host (float 0..1 inputs: clip(x * 255) truncated, test_mvs4.py:262-264)."""
-    kind, images, _, _, _ = _check_images(images)
+    kind, images, _ = _check_images(images)
     if torch.is_tensor(images):
         images = images.detach().cpu().numpy()
     if kind == "u8":
@@ -696,14 +703,10 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same, colours differ
     by the JPEG re-encoding the reference adds."""
     from . import fusion
-    prepare = kw.get("crop_rows") is not None or kw.get("img_wh") is not None
-    if not prepare:                                                          # (these modes take views of different sizes)
-        kind, images, V, H, W = _check_images(images, kw.get("max_h") is not None or kw.get("max_w") is not None)
-    scan = infer_scan(model, images, Ks, Es, depth_ranges, pairs, **kw)
-    if torch.is_tensor(scan.get("images")):
-        kind, images = "u8", scan["images"]                                  # uint8 [V,Hd,Wd,3], already on the device
-    elif prepare:
-        kind, images, V, H, W = _check_images(images)                        # (float32 views already at the target size)
+    inp = plan_inputs(images, Ks, kw.get("max_h"), kw.get("max_w"), kw.get("crop_rows"), kw.get("img_wh"), Es)
+    scan = infer_scan(model, inp.images, Ks, Es, depth_ranges, pairs, **kw)
+    # (prepared: uint8 [V,Hd,Wd,3], already on the device; otherwise the input stack, which has the target size)
+    kind, images = ("u8", scan["images"]) if inp.prepare else (inp.kind, inp.images)
     slot = {int(r): i for i, r in enumerate(scan["ref_views"])}
     fpairs = []
     for r, srcs in scan["pairs"]:

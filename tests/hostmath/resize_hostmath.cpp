@@ -1,14 +1,16 @@
 // Host build of mvster_amd/csrc/resize_math.h -- TEST INFRASTRUCTURE ONLY.
-// A serial loop over a stack of 8-bit images with the very functions resize_pack_images_u8_kernel inlines: the RGB0 float
-// output and the 8-bit output of mvster_resize_pack_images_u8 from the same host-built tables.  Lets the CPU suite check the
-// resampling arithmetic against the NumPy restatements without a GPU, and the GPU suite compare the kernel byte for byte.
+// A serial loop over a stack of 8-bit images with the very functions load_pack_images_u8_kernel inlines: the RGB0 float
+// output and the 8-bit output of mvster_load_pack_images_u8 on full-image windows of one size, from the same host-built
+// tables.  Lets the CPU suite check the resampling arithmetic against the NumPy restatements without a GPU, and the GPU
+// suite compare the kernel byte for byte.
 // Never loaded by the product.  Build: g++ -O2 -shared -fPIC -ffp-contract=off (tests/resize_cases.py).
 #include "../../mvster_amd/csrc/resize_math.h"
 
 extern "C" {
 
-// Layouts as for mvster_resize_pack_images_u8 (include/mvster_hip.h): src [V,Hs,Ws,3], out [V,Hd,Wd,4], out_u8 [V,Hd,Wd,3]
-// (optional).  -> 0, or -1 for a table entry outside the image (the kernel clamps; a test must never rely on that).
+// Layouts as for mvster_load_pack_images_u8 (include/mvster_hip.h) on a packed stack: src [V,Hs,Ws,3], out [V,Hd,Wd,4],
+// out_u8 [V,Hd,Wd,3] (optional).  -> 0, or -1 for a table entry outside the image (the kernel clamps; a test must never
+// rely on that).
 int hm_resize_pack(const unsigned char* src, const int* sx, const float* fx, const int* sy, const float* fy, float* out,
                    unsigned char* out_u8, int V, int Hs, int Ws, int Hd, int Wd) {
     const bool area = Ws == 2 * Wd && Hs == 2 * Hd;

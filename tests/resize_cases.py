@@ -117,7 +117,7 @@ def ref_resize(u8, Hd, Wd):
 
 
 def ref_outputs(u8_stack, Hd, Wd):
-    """What mvster_resize_pack_images_u8 must write for uint8 [V,Hs,Ws,3]: (RGB0 float32 [V,1,Hd,Wd,4], uint8 [V,Hd,Wd,3])."""
+    """What ops.resize_pack_images_u8 must write for uint8 [V,Hs,Ws,3]: (RGB0 float32 [V,1,Hd,Wd,4], uint8 [V,Hd,Wd,3])."""
     V = len(u8_stack)
     out = np.zeros((V, 1, Hd, Wd, 4), dtype=np.float32)
     for v in range(V):

@@ -63,6 +63,32 @@ def test_identity_size_gives_the_bits_of_pack_images_u8(V, H, W):
     assert torch.equal(got, ops.pack_images_u8(dev)) and torch.equal(small, dev)
 
 
+@pytest.mark.parametrize("Hs,Ws", [(128, 192), (130, 197)])
+def test_every_source_route_gives_the_bits_of_the_host_build(hostmath, Hs, Ws):
+    """A list of host views, a host ndarray stack, a CPU tensor stack, a GPU stack and the wrapper on the GPU stack.  Views of
+    128 x 192 x 3 bytes are a multiple of 16 long: the stacks are taken as they lie (one flat upload, or read in place);
+    those of 130 x 197 x 3 are not, and every route gathers them into the ragged buffer."""
+    V, Hd, Wd = 3, 64, 128
+    assert (Hs * Ws * 3 % 16 == 0) == ((Hs, Ws) == (128, 192))
+    u8 = np.random.RandomState(Hs).randint(0, 256, size=(V, Hs, Ws, 3)).astype(np.uint8)
+    want, want_u8 = RC.run_host(hostmath, u8, Hd, Wd, formats.resize_tables(Hs, Ws, Hd, Wd))
+    dev = torch.from_numpy(u8).to(DEV)
+    routes = {"list of host views": (ops.load_pack_images_u8, list(u8)), "host ndarray stack": (ops.load_pack_images_u8, u8),
+              "CPU tensor stack": (ops.load_pack_images_u8, torch.from_numpy(u8)), "GPU stack": (ops.load_pack_images_u8, dev),
+              "wrapper on the GPU stack": (ops.resize_pack_images_u8, dev)}
+    first = None
+    for name, (fn, images) in routes.items():
+        got, got_u8 = fn(images, Hd, Wd, want_u8=True)
+        alone = fn(images, Hd, Wd)
+        torch.cuda.synchronize()
+        bad = int((got.cpu().numpy().view(np.int32) != want.view(np.int32)).sum())
+        bad_u8 = int((got_u8.cpu().numpy() != want_u8).sum())
+        print("%s, %dx%d: differing float words %d, bytes %d" % (name, Hs, Ws, bad, bad_u8))
+        assert bad == 0 and bad_u8 == 0, name
+        first = first or (got, got_u8)
+        assert torch.equal(got, first[0]) and torch.equal(alone, first[0]) and torch.equal(got_u8, first[1]), name
+
+
 def test_resize_pack_rejects_what_the_loader_never_does():
     dev = torch.zeros(1, 128, 128, 3, dtype=torch.uint8, device=DEV)
     for Hd, Wd in ((256, 128), (128, 192), (100, 128), (0, 64)):
@@ -110,6 +136,12 @@ def test_infer_scan_with_scaling_equals_infer_scan_on_host_resized_images(model,
     want_u8 = np.clip(floats.transpose(0, 2, 3, 1) * np.float32(255), 0, 255).astype(np.uint8)
     assert np.array_equal(got["images"].cpu().numpy(), want_u8)
     assert got["stats"]["source_bytes"] == V * Hs * Ws * 3 and got["stats"]["store_bytes"] == scan.store_bytes(V, Hd, Wd)
+    # the other forms the images may come in: the same maps, prepared images, byte count and cameras
+    for form, images in (("a list of views", list(sc["images"])), ("a GPU stack", torch.from_numpy(sc["images"]).to(DEV))):
+        other = scan.infer_scan(model, images, sc["Ks"], *args, max_h=max_h, max_w=max_w)
+        for k in ("depth", "photometric_confidence", "images"):
+            assert torch.equal(other[k], got[k]), (form, k)
+        assert other["stats"]["source_bytes"] == got["stats"]["source_bytes"] and np.array_equal(other["Ks"], got["Ks"]), form
 
 
 def test_reconstruct_scan_and_folder_outputs_with_scaling(model, tmp_path):

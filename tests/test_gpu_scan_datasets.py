@@ -81,9 +81,9 @@ def test_load_pack_equals_resize_linear_on_the_windows(name):
         again = ops.load_pack_images_u8(stack, Hd, Wd, crop=crop, want_u8=True)
         assert torch.equal(again[0], got) and torch.equal(again[1], got_u8)
         if not any(crop):
-            # uniform descriptors, full-image windows: the existing entry, bit for bit
-            old, old_u8 = ops.resize_pack_images_u8(stack, Hd, Wd, want_u8=True)
-            assert torch.equal(got, old) and torch.equal(got_u8, old_u8)
+            # the wrapper for one common size: its descriptors are the uniform ones with full-image windows
+            wrapped, wrapped_u8 = ops.resize_pack_images_u8(stack, Hd, Wd, want_u8=True)
+            assert torch.equal(got, wrapped) and torch.equal(got_u8, wrapped_u8)
 
 
 def test_load_pack_refuses_what_no_loader_does():

@@ -1,13 +1,14 @@
 """The loader's input scaling without a GPU: target sizes and intrinsics, the per-axis tap tables, the host build of
 csrc/resize_math.h against an independent NumPy restatement and ``formats.resize_linear`` (bit for bit, all three),
-``load_eval_sample(resample=True)``, the validation in ``infer_scan`` before any device work, the new ABI entry."""
+``load_eval_sample(resample=True)``, the validation in ``infer_scan`` before any device work, ``scan.plan_inputs`` in the
+``max_h`` / ``max_w`` mode, and that the op's own C entry is gone."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from mvster_amd import formats, scan
+from mvster_amd import formats, ops, scan
 from tests import resize_cases as RC
 from tests import scan_cases as SC
 
@@ -207,23 +208,46 @@ def test_plan_scan_folder_plans_from_the_scaled_intrinsics(tmp_path):
     assert plan.proj["stage4"][plan.view_table[0]].tobytes() == meta["proj_matrices"]["stage4"].tobytes()
 
 
+# ---- the planning function in the max_h / max_w mode ---------------------------------------------------------------------
+@pytest.mark.parametrize("given,want", [((192, 320, 128, 256), (128, 192))] + RC.LOADER_SIZES)
+def test_plan_inputs_with_scaling_gives_the_loaders_size_intrinsics_and_uniform_descriptors(given, want):
+    Hs, Ws, max_h, max_w = given
+    V = 3
+    images = np.zeros((V, Hs, Ws, 3), np.uint8)
+    Ks = SC.synthetic_scan(V, 64, 64, seed=3)["Ks"]
+    inp = scan.plan_inputs(images, Ks, max_h=max_h, max_w=max_w)
+    Hd, Wd, scale_h, scale_w = formats.scale_input_size(Hs, Ws, max_h, max_w)
+    assert (inp.H, inp.W) == (Hd, Wd) == want and inp.crop == (0, 0, 0, 0)
+    assert inp.Ks.tobytes() == formats.scale_intrinsics(Ks, scale_h, scale_w).tobytes() and inp.Ks is not Ks
+    assert (inp.kind, inp.V, inp.sizes, inp.prepare) == ("u8", V, [(Hs, Ws)] * V, True) and inp.images is images
+    assert inp.source_bytes == V * Hs * Ws * 3
+    # the same record from a sequence of views, and from one side alone where that side decides
+    again = scan.plan_inputs(list(images), Ks, max_h=max_h, max_w=max_w)
+    assert (again.H, again.W, again.sizes, again.source_bytes) == (Hd, Wd, inp.sizes, inp.source_bytes)
+    assert again.Ks.tobytes() == inp.Ks.tobytes()
+    # what the launch gets for it: the views where a packed stack has them, one table for all, the area flag only at 2:1
+    desc, tables, total = ops.load_pack_descriptors(inp.sizes, inp.H, inp.W, inp.crop)
+    offs = (desc[:, 0].astype(np.int64) & 0xffffffff) | (desc[:, 1].astype(np.int64) << 32)
+    assert list(offs) == [v * Hs * Ws * 3 for v in range(V)] and total == V * Hs * Ws * 3
+    area = int(Hs == 2 * Hd and Ws == 2 * Wd)
+    assert area == int(given == (2048, 2560, 1024, 1280))
+    assert all(tuple(d[2:10]) == (Hs, Ws, 0, 0, Hs, Ws, 0, area) for d in desc)
+    sx, fx, sy, fy = formats.resize_tables(Hs, Ws, Hd, Wd)
+    one = np.concatenate([sx.view(np.int32), fx.view(np.int32), sy.view(np.int32), fy.view(np.int32)])
+    assert np.array_equal(tables, one if (Hs, Ws) != (Hd, Wd) else one[:0])  # (the identity size reads no table)
+
+
 # ---- ABI ---------------------------------------------------------------------------------------------------------------------
 def test_resize_entry_is_declared_bound_and_exported():
+    """The op kept its name; its C entry went when the launch became mvster_load_pack_images_u8's (whose error returns
+    tests/test_scan_datasets_cpu.py pins)."""
     import __graft_entry__ as ge
     ge.build()
-    from mvster_amd import _lib, ops
+    from mvster_amd import _lib
     lib = _lib.load()
     header = open(os.path.join(RC.ROOT, "include", "mvster_hip.h")).read()
     name = "mvster_resize_pack_images_u8"
-    assert name in _lib.SIGNATURES and hasattr(lib, name) and ("int %s(" % name) in header
-    fn = lib.mvster_resize_pack_images_u8
-    a, b, c, d = 1 << 32, 1 << 33, 1 << 34, 1 << 35                          # never dereferenced: validation comes first
-    assert fn(None, b, c, d, 1, 128, 128, 64, 64, None) == _lib.ERR_NULL
-    assert fn(a, None, c, d, 1, 128, 128, 64, 64, None) == _lib.ERR_NULL
-    assert fn(a, b, None, d, 1, 128, 128, 64, 64, None) == _lib.ERR_NULL
-    for V, Hs, Ws, Hd, Wd in ((0, 128, 128, 64, 64), (1, 0, 128, 64, 64), (1, 128, -1, 64, 64), (1, 128, 128, 0, 64),
-                              (1, 128, 128, 64, 96), (1, 128, 128, 100, 64), (1, 64, 128, 128, 64), (1, 128, 64, 64, 128)):
-        assert fn(a, b, c, None, V, Hs, Ws, Hd, Wd, None) == _lib.ERR_SHAPE, (V, Hs, Ws, Hd, Wd)
+    assert name not in _lib.SIGNATURES and not hasattr(lib, name) and name not in header
     assert callable(ops.resize_pack_images_u8)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.resize_pack_images_u8(torch.zeros(1, 64, 64, 3, dtype=torch.uint8), 64, 64)

@@ -123,6 +123,10 @@ def test_descriptor_and_table_builder():
         want = np.concatenate([sx.view(np.int32), fx.view(np.int32), sy.view(np.int32), fy.view(np.int32)])
         assert np.array_equal(tables[t:t + per], want)
         assert sx.max() < sizes[v][1] and sy.max() < sizes[v][0]               # tap indices relative to the window, inside it
+    # the builder is memoised; what a caller does to its arrays does not reach the next one
+    desc[:], tables[:] = -1, -1
+    again = ops.load_pack_descriptors(sizes, Hd, Wd)
+    assert again[0][0, 2] == 150 and again[1].min() >= 0 and again[2] == total
     # a crop: the window moves, the taps are those of the window's size; a pure crop has no table at all
     desc, tables, total = ops.load_pack_descriptors([(120, 131)] * 4, 64, 128, crop=(28, 28, 1, 2))
     assert tables.size == 0 and total == 4 * ((120 * 131 * 3 + 15) // 16 * 16)
@@ -172,7 +176,8 @@ def test_load_pack_entry_is_declared_bound_exported_and_validates_on_the_host():
         bad[v, word] = value
         return bad
     for what, bad in (("image past the buffer", with_(1, 0, (total // 16) * 16)), ("misaligned offset", with_(1, 0, desc[1, 0] + 4)),
-                      ("negative offset", with_(0, 1, -1)), ("Hs 0", with_(0, 2, 0)), ("image larger than the buffer", with_(0, 2, 1 << 20)),
+                      ("negative offset", with_(0, 1, -1)), ("Hs 0", with_(0, 2, 0)), ("Ws -1", with_(0, 3, -1)),
+                      ("image larger than the buffer", with_(0, 2, 1 << 20)),
                       ("window below the image", with_(0, 4, 1)), ("window right of the image", with_(0, 5, 1)),
                       ("negative y0", with_(0, 4, -1)), ("window taller than the image", with_(0, 6, 151)),
                       ("enlarging in y", with_(0, 6, 63)), ("enlarging in x", with_(0, 7, 127)),
