@@ -538,6 +538,26 @@ int mvster_fused_adam(const void* const* params, const void* const* grads, const
  * from their parameters after an optimizer update (host-side plumbing: the reference's layers read the parameters directly). */
 int mvster_gather_batch(const void* descs, int ndesc, int total_blocks, void* stream);
 
+/* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
+
+/* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,
+ * gt, mask [N,HW] (mask > 0.5 = valid), scale [N] or NULL, thres [K] on the HOST (1 <= K <= 8).  For a valid pixel
+ * e = |est*s - gt*s| with s = scale[n] (|est - gt| without scale), every operation rounded on its own ->
+ * partial [N][mvster_depth_metrics_slots(HW)][2+K] doubles (scratch), raw [N][2+K] doubles = valid pixels, sum of e
+ * (fp64), #{e > thres[k]} (strict, IEEE: a NaN error counts for no threshold and makes the sum NaN, inf counts for all),
+ * out [1+K] floats = abs_depth_error, thres_k errors: per image (float)(x / valid) with the quotient in double, then the
+ * fp32 mean over the images in image order (compute_metrics_for_each_image, :126-136); an image without a valid pixel
+ * gives NaN, like torch.mean of an empty tensor.  Two launches, no atomics: bit-reproducible. */
+int mvster_depth_metrics_slots(long hw);
+int mvster_depth_metrics(const float* est, const float* gt, const float* mask, const float* scale, const float* thres, int K,
+                         int N, long HW, double* partial, double* raw, float* out, void* stream);
+
+/* DictAverageMeter.update (utils.py:108-119) on the device: sums [n] doubles += row [n] floats, count [1] += 1 (Python
+ * floats are doubles: the same sums in the same order); mvster_scalar_reset zeroes both (a kernel, not a memset node).
+ * One single-workgroup launch each, reading and writing only through the arguments: capturable. */
+int mvster_scalar_accumulate(const float* row, int n, double* sums, long* count, void* stream);
+int mvster_scalar_reset(double* sums, int n, long* count, void* stream);
+
 /* Name of the kernel the most recent mvster_conv_mfma / mvster_conv_small / mvster_deconv_small / mvster_conv_wgrad /
  * mvster_warp_agg_fwd / mvster_warp_agg_bwd (first pass) call on the calling host thread launched, in the profiler's spelling with template arguments (e.g. "conv_lds_kernel<2, 1, 3, 1, 3>");
  * "" before the first call.  The pointer stays valid for the life of the library.  (bench.py attributes HIP-event timings

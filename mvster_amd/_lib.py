@@ -90,6 +90,10 @@ SIGNATURES = {
     "mvster_geo_scene_blocks": [_i, _i, _i],
     "mvster_geo_scene_filter": [_f] * 13 + [_i] * 5 + [_fl, _i, _fl, _fl, _f],
     "mvster_geo_scene_emit": [_f] * 5 + [_i, _f, _f, _f, _l, _i, _i, _i, _i, _f],
+    "mvster_depth_metrics_slots": [_l],
+    "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
+    "mvster_scalar_accumulate": [_f, _i, _f, _f, _f],
+    "mvster_scalar_reset": [_f, _i, _f, _f],
     "mvster_mfma_probe": [_f, _f, _f, _f],
     "mvster_gather_batch": [_f, _i, _i, _f],
     "mvster_last_kernel": [],

@@ -5,6 +5,7 @@ returns freshly allocated outputs.  Names and argument meaning follow the refere
 functions in models/mvs4net_utils.py; shapes at this level use the reference's layouts
 (NCHW / NCDHW) unless the name says ``_cl`` (channels-last).
 """
+import ctypes
 import functools
 
 import torch
@@ -1184,3 +1185,60 @@ def fine_weights_bwd(wo, wi, bi, g_wg, g_wc, g_vb):
     _lib.check(_lib.load().mvster_fine_weights_bwd(_ptr(wo), _ptr(wi), _ptr(bi), _ptr(g_wg), _ptr(g_wc), _ptr(g_vb), _ptr(g_wo),
                                                    _ptr(g_wi), _ptr(g_bi), CO, CM, CI, _stream()), "fine_weights_bwd")
     return g_wo, g_wi, g_bi
+
+
+# ---- validation pass (csrc/val_ops.hip) ---------------------------------------------------------------------------------
+def depth_metrics(est, gt, mask, thresholds=(2, 4, 8), scale=None):
+    """The depth metrics of a batch (utils.py:125-159) without boolean-mask gathers: est, gt, mask [N,H,W] (mask > 0.5 =
+    valid), scale [N] or None -> (out [1+K] fp32 = abs_depth_error and the error ratio above every threshold, per image
+    then averaged; raw [N,2+K] fp64 = valid pixels, sum of |est*s - gt*s|, errors above every threshold).  Two launches,
+    no synchronisation."""
+    for t, n in ((est, "est"), (gt, "gt"), (mask, "mask"), (scale, "scale")):
+        _chk(t, "depth_metrics:" + n)
+    if est.dim() != 3 or tuple(gt.shape) != tuple(est.shape) or tuple(mask.shape) != tuple(est.shape):
+        raise RuntimeError("depth_metrics: est, gt and mask must be [N,H,W] tensors of one shape")
+    N, H, W = est.shape
+    K = len(thresholds)
+    if not 1 <= K <= 8:
+        raise RuntimeError("depth_metrics: 1 to 8 thresholds, got %d" % K)
+    if N <= 0 or H * W <= 0:
+        raise RuntimeError("depth_metrics: empty input %s" % (tuple(est.shape),))
+    if scale is not None and tuple(scale.shape) != (N,):
+        raise RuntimeError("depth_metrics: scale must hold one value per image")
+    for t in (gt, mask, scale):
+        if t is not None and t.device != est.device:
+            raise RuntimeError("depth_metrics: tensors on different devices")
+    lib = _lib.load()
+    thres = (ctypes.c_float * K)(*[float(t) for t in thresholds])
+    partial = torch.empty(N * lib.mvster_depth_metrics_slots(H * W) * (2 + K), device=est.device, dtype=torch.float64)
+    raw = torch.empty(N, 2 + K, device=est.device, dtype=torch.float64)
+    out = torch.empty(1 + K, device=est.device, dtype=torch.float32)
+    rc = lib.mvster_depth_metrics(_ptr(est), _ptr(gt), _ptr(mask), _ptr(scale), ctypes.cast(thres, ctypes.c_void_p), K, N, H * W,
+                                  _ptr(partial), _ptr(raw), _ptr(out), _stream())
+    _lib.check(rc, "depth_metrics")
+    return out, raw
+
+
+def _chk_meter(sums, count, name):
+    if not (sums.is_cuda and count.is_cuda and sums.device == count.device):
+        raise RuntimeError("mvster_amd.ops.%s: expected GPU tensors on one device (the HIP path has no CPU fallback)" % name)
+    if sums.dtype != torch.float64 or count.dtype != torch.int64:
+        raise RuntimeError("mvster_amd.ops.%s: sums must be float64 and count int64, got %s / %s" % (name, sums.dtype, count.dtype))
+    if not (sums.is_contiguous() and count.is_contiguous()) or sums.dim() != 1 or count.numel() != 1 or sums.numel() == 0:
+        raise RuntimeError("mvster_amd.ops.%s: sums must be a contiguous [n] tensor and count hold one element" % name)
+
+
+def scalar_accumulate(row, sums, count):
+    """``DictAverageMeter.update`` (utils.py:108-119) on the device, in place: sums [n] fp64 += row [n] fp32, count [1]
+    int64 += 1.  One launch, capturable."""
+    _chk(row, "scalar_accumulate:row")
+    _chk_meter(sums, count, "scalar_accumulate")
+    if row.dim() != 1 or row.numel() != sums.numel() or row.device != sums.device:
+        raise RuntimeError("scalar_accumulate: row must be a [%d] tensor on the device of sums" % sums.numel())
+    _lib.check(_lib.load().mvster_scalar_accumulate(_ptr(row), row.numel(), _ptr(sums), _ptr(count), _stream()), "scalar_accumulate")
+
+
+def scalar_reset(sums, count):
+    """Zero the running sums and the count of ``scalar_accumulate`` (one launch; no memset node)."""
+    _chk_meter(sums, count, "scalar_reset")
+    _lib.check(_lib.load().mvster_scalar_reset(_ptr(sums), sums.numel(), _ptr(count), _stream()), "scalar_reset")
