@@ -552,11 +552,28 @@ int mvster_depth_metrics_slots(long hw);
 int mvster_depth_metrics(const float* est, const float* gt, const float* mask, const float* scale, const float* thres, int K,
                          int N, long HW, double* partial, double* raw, float* out, void* stream);
 
+/* Blend_loss's error figures (MVS4Net.py:202-205) without a boolean-mask gather, pooled over ALL valid pixels of the batch
+ * (not per image): arguments, e and the scratch as for mvster_depth_metrics; thres [K] on the HOST is read before the call
+ * returns (the kernels get the values) -> raw [N][2+K] doubles = valid pixels, sum of e (fp64), #{e <= thres[k]} (counted
+ * as such, IEEE: a NaN error at a valid pixel is in the denominator only, +inf is at-or-below nothing),
+ * out [1+K] floats: with the columns of raw summed over the images in image order (counts exact, the sum fp64),
+ * epe = (float)(sum_e / valid) and err_k = fl32(fl32(le_k / valid) * 100): the quotients in double, rounded once to fp32,
+ * then an fp32 multiply; a batch without a valid pixel gives NaN.  Two launches, no atomics: bit-reproducible, whatever the
+ * planes' alignment. */
+int mvster_pooled_metrics(const float* est, const float* gt, const float* mask, const float* scale, const float* thres, int K,
+                          int N, long HW, double* partial, double* raw, float* out, void* stream);
+
 /* DictAverageMeter.update (utils.py:108-119) on the device: sums [n] doubles += row [n] floats, count [1] += 1 (Python
  * floats are doubles: the same sums in the same order); mvster_scalar_reset zeroes both (a kernel, not a memset node).
  * One single-workgroup launch each, reading and writing only through the arguments: capturable. */
 int mvster_scalar_accumulate(const float* row, int n, double* sums, long* count, void* stream);
 int mvster_scalar_reset(double* sums, int n, long* count, void* stream);
+
+/* A training step's scalars, each a device tensor of its own, into one row and into the running sums in ONE launch: ptrs [n]
+ * on the HOST holds the device address of every scalar (1 <= n <= 32, none NULL; read before the call returns) ->
+ * row [n] floats = the scalars, sums [n] doubles += them, count [1] += 1 -- what torch.stack followed by
+ * mvster_scalar_accumulate leaves.  Capturable: the addresses are kernel arguments. */
+int mvster_scalar_gather_accumulate(const void* const* ptrs, int n, float* row, double* sums, long* count, void* stream);
 
 /* Name of the kernel the most recent mvster_conv_mfma / mvster_conv_small / mvster_deconv_small / mvster_conv_wgrad /
  * mvster_warp_agg_fwd / mvster_warp_agg_bwd (first pass) call on the calling host thread launched, in the profiler's spelling with template arguments (e.g. "conv_lds_kernel<2, 1, 3, 1, 3>");

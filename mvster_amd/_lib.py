@@ -92,7 +92,9 @@ SIGNATURES = {
     "mvster_geo_scene_emit": [_f] * 5 + [_i, _f, _f, _f, _l, _i, _i, _i, _i, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
+    "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_scalar_accumulate": [_f, _i, _f, _f, _f],
+    "mvster_scalar_gather_accumulate": [_f, _i, _f, _f, _f, _f],
     "mvster_scalar_reset": [_f, _i, _f, _f],
     "mvster_mfma_probe": [_f, _f, _f, _f],
     "mvster_gather_batch": [_f, _i, _i, _f],

@@ -33,8 +33,10 @@ __host__ __device__ inline long slot_len(long HW, int slots) { return ((HW + slo
 // One workgroup = (image n, slot c): pixels [c * len, min((c + 1) * len, HW)) of image n, in rounds of 1024 with lane t on
 // pixels 4t .. 4t + 3 of a round -- one float4 per plane when `vec` (HW % 4 == 0 and 16-byte aligned planes), four guarded
 // scalar loads otherwise: the same pixels in the same order either way, so the sums do not depend on the alignment.
-// partial [N][slots][2 + K] doubles: valid pixels, sum of e, #{e > t[k]}; fixed order (lane, wave shuffles, the four waves
-// through LDS), no atomics.  An empty slot (c * len >= HW) writes zeros.
+// partial [N][slots][2 + K] doubles: valid pixels, sum of e, #{e > t[k]} (LE: #{e <= t[k]} -- counted, not derived as valid
+// minus above: a NaN error is neither); fixed order (lane, wave shuffles, the four waves through LDS), no atomics.  An empty
+// slot (c * len >= HW) writes zeros.
+template <bool LE>
 __global__ void __launch_bounds__(256) depth_metrics_partial_kernel(const float* __restrict__ est, const float* __restrict__ gt,
                                                                     const float* __restrict__ mask,
                                                                     const float* __restrict__ scale, Thresholds th, int K,
@@ -76,7 +78,7 @@ __global__ void __launch_bounds__(256) depth_metrics_partial_kernel(const float*
             cnt[0] += 1u;
             sum += (double)e;
 #pragma unroll
-            for (int k = 0; k < kMaxThres; ++k) cnt[1 + k] += (k < K && e > th.t[k]) ? 1u : 0u;
+            for (int k = 0; k < kMaxThres; ++k) cnt[1 + k] += (k < K && (LE ? e <= th.t[k] : e > th.t[k])) ? 1u : 0u;
         }
     }
     sum = wave_sum(sum);
@@ -124,6 +126,49 @@ __global__ void __launch_bounds__(256) depth_metrics_finish_kernel(const double*
     }
 }
 
+// Blend_loss's error figures (MVS4Net.py:202-205), pooled over the batch: raw as above (its threshold columns hold
+// #{e <= t[k]}); then, by thread j <= K, the columns summed over the images in image order (counts exact, the error sum
+// fp64) and out [1 + K] = epe = (float)(sum_e / count) -- the quotient in double, rounded once -- and err_k =
+// fl32(fl32(count_le_k / count) * 100): (err <= t).float().mean() * 100.  A batch without a valid pixel gives 0 / 0 = NaN.
+__global__ void __launch_bounds__(256) pooled_metrics_finish_kernel(const double* __restrict__ partial, int N, int K, int slots,
+                                                                    double* __restrict__ raw, float* __restrict__ out) {
+    const int cols = 2 + K;
+    for (int i = threadIdx.x; i < N * cols; i += 256) {
+        const int n = i / cols, j = i - n * cols;
+        const double* p = partial + (long)n * slots * cols + j;
+        double s = 0.0;
+        for (int c = 0; c < slots; ++c) s += p[(long)c * cols];
+        raw[i] = s;
+    }
+    __syncthreads();                 // (raw written above by this workgroup: visible to it after the barrier)
+    if (threadIdx.x <= K) {
+        const int j = threadIdx.x;
+        double count = 0.0, x = 0.0;
+        for (int n = 0; n < N; ++n) {
+            count += raw[(long)n * cols];
+            x += raw[(long)n * cols + 1 + j];
+        }
+        const float q = (float)(x / count);
+        out[j] = j == 0 ? q : __fmul_rn(q, 100.0f);
+    }
+}
+
+constexpr int kMaxGather = 32;
+struct ScalarPtrs { const float* p[kMaxGather]; };
+
+// row[i] = *src.p[i], sums[i] += row[i] in double, count += 1: a step's scalars, scattered over as many device tensors,
+// into one row and into the running sums in one launch
+__global__ void __launch_bounds__(64) scalar_gather_accumulate_kernel(ScalarPtrs src, int n, float* __restrict__ row,
+                                                                      double* __restrict__ sums, long* __restrict__ count) {
+    const int i = threadIdx.x;
+    if (i < n) {
+        const float v = *src.p[i];
+        row[i] = v;
+        sums[i] += (double)v;
+    }
+    if (i == 0) count[0] += 1L;
+}
+
 // sums[i] += row[i] in double, count += 1; `reset`: both to zero instead (row is not read)
 __global__ void __launch_bounds__(64) scalar_accumulate_kernel(const float* __restrict__ row, int n, double* __restrict__ sums,
                                                                long* __restrict__ count, int reset) {
@@ -159,9 +204,30 @@ extern "C" int mvster_depth_metrics(const float* est, const float* gt, const flo
     for (int k = 0; k < kMaxThres; ++k) th.t[k] = k < K ? thres[k] : 0.0f;
     const int vec = (HW % 4 == 0) && ((((uintptr_t)est | (uintptr_t)gt | (uintptr_t)mask) & 15) == 0);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(depth_metrics_partial_kernel, dim3((unsigned)(N * slots)), dim3(256), 0, s, est, gt, mask, scale, th, K, HW,
-                       slots, vec, partial);
+    hipLaunchKernelGGL(depth_metrics_partial_kernel<false>, dim3((unsigned)(N * slots)), dim3(256), 0, s, est, gt, mask, scale, th,
+                       K, HW, slots, vec, partial);
     hipLaunchKernelGGL(depth_metrics_finish_kernel, dim3(1), dim3(256), 0, s, partial, N, K, slots, raw, out);
+    return mv_check_launch();
+}
+
+// Blend_loss's epe / err<t> (MVS4Net.py:202-205), pooled over all valid pixels of the batch: arguments as
+// mvster_depth_metrics, the thresholds BY VALUE (thres [K] on the host is read before the call returns) ->
+//   raw [N][2 + K] doubles: valid pixels, sum of e = |est*s - gt*s| over them, #{e <= thres[k]}
+//   out [1 + K] floats: epe, err_k in per cent (see the finish kernel)
+// Two launches, no atomics: bit-reproducible.
+extern "C" int mvster_pooled_metrics(const float* est, const float* gt, const float* mask, const float* scale, const float* thres,
+                                     int K, int N, long HW, double* partial, double* raw, float* out, void* stream) {
+    if (!est || !gt || !mask || !thres || !partial || !raw || !out) return MVSTER_ERR_NULL;
+    if (K < 1 || K > kMaxThres || N <= 0 || HW <= 0) return MVSTER_ERR_SHAPE;
+    const int slots = mvster_depth_metrics_slots(HW);
+    if ((long)N * slots >= (1L << 31) || (long)N * (2 + kMaxThres) >= (1L << 31)) return MVSTER_ERR_SHAPE;
+    Thresholds th;
+    for (int k = 0; k < kMaxThres; ++k) th.t[k] = k < K ? thres[k] : 0.0f;
+    const int vec = (HW % 4 == 0) && ((((uintptr_t)est | (uintptr_t)gt | (uintptr_t)mask) & 15) == 0);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(depth_metrics_partial_kernel<true>, dim3((unsigned)(N * slots)), dim3(256), 0, s, est, gt, mask, scale, th,
+                       K, HW, slots, vec, partial);
+    hipLaunchKernelGGL(pooled_metrics_finish_kernel, dim3(1), dim3(256), 0, s, partial, N, K, slots, raw, out);
     return mv_check_launch();
 }
 
@@ -171,6 +237,22 @@ extern "C" int mvster_scalar_accumulate(const float* row, int n, double* sums, l
     if (!row || !sums || !count) return MVSTER_ERR_NULL;
     if (n <= 0) return MVSTER_ERR_SHAPE;
     hipLaunchKernelGGL(scalar_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, row, n, sums, count, 0);
+    return mv_check_launch();
+}
+
+// A training step's scalars into one row and into the running sums, one launch: ptrs [n] on the HOST = the device address of
+// every scalar (1 <= n <= 32; read before the call returns) -> row [n] floats = the scalars, sums [n] doubles += them,
+// count [1] += 1: torch.stack + mvster_scalar_accumulate, the same sums.  Reads and writes only through its arguments.
+extern "C" int mvster_scalar_gather_accumulate(const void* const* ptrs, int n, float* row, double* sums, long* count,
+                                               void* stream) {
+    if (!ptrs || !row || !sums || !count) return MVSTER_ERR_NULL;
+    if (n <= 0 || n > kMaxGather) return MVSTER_ERR_SHAPE;
+    ScalarPtrs src;
+    for (int i = 0; i < kMaxGather; ++i) {
+        src.p[i] = i < n ? (const float*)ptrs[i] : nullptr;
+        if (i < n && !src.p[i]) return MVSTER_ERR_NULL;
+    }
+    hipLaunchKernelGGL(scalar_gather_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, n, row, sums, count);
     return mv_check_launch();
 }
 

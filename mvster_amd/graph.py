@@ -325,6 +325,33 @@ class GraphedForward:
         return self.outputs
 
 
+def graph_kernel_nodes(graph):
+    """(kernel nodes, all nodes) of a captured ``torch.cuda.CUDAGraph`` that was built with ``keep_graph=True``, asked of
+    the HIP runtime this process runs on (``hipGraphGetNodes``): the launch count of one replay, exactly -- the profiler's
+    count of device activities of an eager run is not reproducible run to run.  Measurement and tests only."""
+    import ctypes
+    paths = sorted({ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln}, key=lambda p: "torch" not in p)
+    if not paths:
+        raise RuntimeError("graph_kernel_nodes: no HIP runtime is loaded in this process")
+    hip = ctypes.CDLL(paths[0])
+    hip.hipGraphGetNodes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    hip.hipGraphNodeGetType.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    handle = ctypes.c_void_p(graph.raw_cuda_graph())
+    n = ctypes.c_size_t(0)
+    if hip.hipGraphGetNodes(handle, None, ctypes.byref(n)) != 0:
+        raise RuntimeError("graph_kernel_nodes: hipGraphGetNodes failed")
+    nodes = (ctypes.c_void_p * max(n.value, 1))()
+    if hip.hipGraphGetNodes(handle, nodes, ctypes.byref(n)) != 0:
+        raise RuntimeError("graph_kernel_nodes: hipGraphGetNodes failed")
+    kernels = 0
+    for node in list(nodes)[:n.value]:
+        kind = ctypes.c_int(-1)
+        if hip.hipGraphNodeGetType(ctypes.c_void_p(node), ctypes.byref(kind)) != 0:
+            raise RuntimeError("graph_kernel_nodes: hipGraphNodeGetType failed")
+        kernels += int(kind.value == 0)                 # hipGraphNodeTypeKernel
+    return kernels, int(n.value)
+
+
 class GraphedTrainStep:
     """One whole training step -- forward, loss, backward, optimizer update -- captured in a hipGraph.
 
@@ -342,6 +369,17 @@ class GraphedTrainStep:
 
     The graph updates the optimizer's state tensors by address: ``optimizer.load_state_dict`` replaces them (and
     ``optim.FusedAdam``'s flat buffers), so the step must be rebuilt after it -- a replay after it raises.
+
+    ``summary=True``: the step also forms what the reference's ``train_sample`` logs (train_mvs4.py:220-236) -- inside the
+    captured sequence, after the loss forward, under ``no_grad``, on the step's main stream, with no host synchronisation:
+    ``row`` (static [17] fp32, ``names`` = ``validate.SCALAR_NAMES``: the loss function's four returns as this step
+    computed them, then ``ops.depth_metrics`` of ``outputs["depth"]`` against the last stage's ground truth and mask; a
+    loss function with ``Blend_loss``'s 7 returns adds ``epe``, ``err3``, ``err1``: 20), the running sums ``sums`` (fp64)
+    / ``count`` (int64) on the device, and ``depth_est``, the finest depth map of the last step (the only output kept
+    alive).  Three launches more per step: the metrics' two and one that gathers the scalars by address into the row and
+    adds them to the sums (``mvster_scalar_gather_accumulate``).  ``summary_mean()`` is the one synchronising call;
+    with several ranks it holds the one collective (the reference reduces every step's scalars).  The loss function must
+    return ``(loss, [4], [4], [4])`` or that plus three scalars for a four-stage model: anything else raises here.
     """
 
     # HIP streams the postponed weight-gradient kernels are spread over (train_ops.deferred_wgrad_finish).  They are persistent
@@ -357,7 +395,7 @@ class GraphedTrainStep:
     wgrad_overlap = False           # True: the kernels run on one side stream beside the backward chain, not after it
 
     def __init__(self, model, optimizer, loss_fn, imgs, proj_matrices, depth_values, depth_gt_ms, mask_ms, warmup=3,
-                 grad_sync=None, capture=True):
+                 grad_sync=None, capture=True, summary=False):
         """``capture=False``: the same object without the hipGraph -- every call runs the identical sequence (static input
         buffers, zero_grad, forward, loss, backward, ``grad_sync.sync()``, optimizer step) eagerly.  That is what the
         multi-process CPU test drives over gloo (tests/test_shard_cpu.py: two ranks end to end against DistributedDataParallel);
@@ -380,16 +418,26 @@ class GraphedTrainStep:
         from . import train_ops
         self._cache = train_ops.CACHE
         self._cell = [0]
+        self.summary = bool(summary)
         if not capture:
+            if self.summary:
+                self._summary_init()
             self.loss = None
             return
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
+        if self.summary:
+            self._summary_init(side)                   # (on the warm-up's stream: one stream's cached blocks, not two)
         with torch.cuda.stream(side):
+            if self.summary:                           # the warm-up steps leave the running sums at zero
+                self._acc = torch.zeros_like(self.sums), torch.zeros_like(self.count)
             for _ in range(warmup):                    # builds the cached layers and the optimizer state, warms the allocator
                 self._step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        if self.summary:
+            self._acc = self.sums, self.count          # (recorded by the capture, which executes nothing)
+            self.depth_est = None
         # the ~130 per-layer weight refreshes a captured step would record become one launch (train_ops._LayerCache)
         # the captured optimizer update moves the parameters (and BatchNorm's running statistics) without touching their
         # version counters: one epoch cell for everything this step owns, bumped after every replay
@@ -428,6 +476,94 @@ class GraphedTrainStep:
         except Exception:
             pass
 
+    # ---- summary=True: train_sample's scalar_outputs inside the step ----------------------------------------------------
+    BLEND_NAMES = ("epe", "err3", "err1")
+
+    @staticmethod
+    def _describe(res):
+        if torch.is_tensor(res):
+            return "a tensor of shape %s" % (tuple(res.shape),)
+        if isinstance(res, (tuple, list)):
+            return "a %s of %d: (%s)" % (type(res).__name__, len(res), ", ".join(
+                ("a %s of %d" % (type(r).__name__, len(r))) if isinstance(r, (tuple, list)) else
+                ("a tensor of shape %s" % (tuple(r.shape),)) if torch.is_tensor(r) else type(r).__name__ for r in res))
+        return type(res).__name__
+
+    def _scalars_of(self, out, res):
+        """The loss function's returns as the flat list of the row's first 13 (or 13 + 3) one-element tensors."""
+        def one(t):
+            return torch.is_tensor(t) and t.numel() == 1 and t.is_cuda and t.dtype == torch.float32
+        stages = len([k for k in out.keys() if "stage" in k]) if isinstance(out, dict) else -1
+        ok = (stages == 4 and "depth" in out and isinstance(res, (tuple, list)) and len(res) in (4, 7) and one(res[0])
+              and all(isinstance(r, (tuple, list)) and len(r) == 4 and all(one(t) for t in r) for r in res[1:4])
+              and all(one(t) for t in res[4:]))
+        if not ok:
+            raise TypeError("GraphedTrainStep(summary=True): the loss function must return (loss, [4 d_loss], [4 c_loss], "
+                            "[4 range_err_ratio]) or Blend_loss's seven (that and epe, err3, err1), one-element fp32 device "
+                            "tensors over the 4 stages of the model's outputs; it returned %s for outputs of %d stages"
+                            % (self._describe(res), stages))
+        return [res[0]] + list(res[1]) + list(res[2]) + list(res[3]), list(res[4:])
+
+    def _summary_init(self, stream=None):
+        """One forward and loss on the construction batch, no backward (BatchNorm's running statistics put back): what the
+        loss function returns decides the names; a loss function of another form raises before anything is built."""
+        import contextlib
+        from .validate import SCALAR_NAMES
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            bufs = [(b, b.detach().clone()) for b in self.model.buffers()]
+            out = self.model(self.imgs, self.proj, self.depth_values)
+            res = self.loss_fn(out, self.gt, self.mask)
+            _, extra = self._scalars_of(out, res)
+            del out, res
+            with torch.no_grad():
+                for b, keep in bufs:
+                    b.copy_(keep)
+            del bufs
+        self.names = tuple(SCALAR_NAMES) + (self.BLEND_NAMES if extra else ())
+        dev = self.depth_values.device
+        self.row = torch.zeros(len(self.names), dtype=torch.float32, device=dev)
+        self.sums = torch.empty(len(self.names), dtype=torch.float64, device=dev)
+        self.count = torch.empty(1, dtype=torch.int64, device=dev)
+        self._acc = self.sums, self.count
+        self.depth_est = None
+        self.summary_reset()
+
+    def _summarise(self, out, res):
+        from . import ops
+        from .validate import THRESHOLDS, _planes
+        first, extra = self._scalars_of(out, res)
+        if len(first) + 4 + len(extra) != len(self.names):
+            raise TypeError("GraphedTrainStep(summary=True): the loss function returned %s, not what it returned at "
+                            "construction (%d scalars)" % (self._describe(res), len(self.names)))
+        with torch.no_grad():
+            last = "stage%d" % len(self.gt)
+            depth = out["depth"].detach()
+            metrics, _ = ops.depth_metrics(*_planes(depth, self.gt[last], self.mask[last]), thresholds=THRESHOLDS)
+            ops.scalar_gather_accumulate([t.detach() for t in first] + list(metrics.unbind(0)) + [t.detach() for t in extra],
+                                         self.row, *self._acc)
+        self.depth_est = depth             # (only this of the outputs stays alive: the rest of the pool's blocks are reused)
+
+    def summary_reset(self):
+        """Zero the running sums and the count (one launch)."""
+        from . import ops
+        ops.scalar_reset(self.sums, self.count)
+
+    def summary_mean(self, group=None):
+        """The averages of the rows since ``summary_reset()`` as ``{name: float}``: the one synchronising call -- one
+        read-back of ``sums || count``, after ONE all-reduce of it when ``group`` (None: the default group of an initialised
+        torch.distributed) has more than one rank (``validate.reduce_scalar_sums``); no collective per step."""
+        from .validate import reduce_scalar_sums
+        return reduce_scalar_sums(self.sums, self.count, group, names=self.names)
+
+    def last_images(self):
+        """train_sample's ``image_outputs`` of the last step (train_mvs4.py:238-244): ``depth_est`` (masked),
+        ``depth_est_nomask`` (a copy), ``errormap`` as fresh device tensors -- tensor expressions outside the graph."""
+        if not self.summary or self.depth_est is None:
+            raise RuntimeError("GraphedTrainStep.last_images: needs summary=True and a step that has run")
+        last = "stage%d" % len(self.gt)
+        depth, gt, mask = self.depth_est, self.gt[last], self.mask[last]
+        return {"depth_est": depth * mask, "depth_est_nomask": depth.clone(), "errormap": (depth - gt).abs() * mask}
+
     def _step(self):
         # grads are re-created by every backward: inside the capture they come from the graph's private pool, so a replay
         # writes them in place and no zero-fill / accumulate kernels are recorded
@@ -439,6 +575,8 @@ class GraphedTrainStep:
             out = self.model(self.imgs, self.proj, self.depth_values)
             res = self.loss_fn(out, self.gt, self.mask)
             loss = res[0] if isinstance(res, (tuple, list)) else res
+            if self.summary:
+                self._summarise(out, res)
             # (nothing reads a weight gradient before the backward pass is over -- the bucketed all-reduce and the optimizer
             #  come after it -- so the 64 finishing launches of the weight-gradient kernels are issued as one)
             from .train_ops import deferred_wgrad_finish

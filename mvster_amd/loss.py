@@ -170,7 +170,19 @@ def Blend_loss(inputs, depth_gt_ms, mask_ms, **kwargs):
     if total is None:
         total = torch.zeros((), dtype=torch.float32, device=mask_ms["stage1"].device)
     key = last
+    depth = inputs[key]["depth"]
+    if depth.is_cuda:
+        # one fused reduction (mvster_pooled_metrics) instead of the boolean-mask gather below, which synchronises and cannot
+        # be captured: the same fp32 errors (one multiply per operand), fp64 sums
+        from . import ops
+        with torch.no_grad():
+            scale = (128 / (depth_max - depth_min)).to(depth.device, torch.float32).reshape(-1)
+            if scale.numel() != depth.shape[0]:
+                scale = scale.expand(depth.shape[0])
+            out, _ = ops.pooled_metrics(depth.detach().to(torch.float32).contiguous(), depth_gt_ms[key].to(torch.float32).contiguous(),
+                                        mask_ms[key].to(torch.float32).contiguous(), (3, 1), scale.contiguous())
+        return total, l1s, ots, ranges, out[0], out[1], out[2]
     mask = mask_ms[key] > 0.5
     scale = 128 / (depth_max - depth_min)[:, None, None]
-    err = torch.abs(inputs[key]["depth"] * scale - depth_gt_ms[key] * scale)[mask]
+    err = torch.abs(depth * scale - depth_gt_ms[key] * scale)[mask]
     return total, l1s, ots, ranges, err.mean(), (err <= 3).float().mean() * 100, (err <= 1).float().mean() * 100

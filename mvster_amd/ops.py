@@ -1188,35 +1188,48 @@ def fine_weights_bwd(wo, wi, bi, g_wg, g_wc, g_vb):
 
 
 # ---- validation pass (csrc/val_ops.hip) ---------------------------------------------------------------------------------
-def depth_metrics(est, gt, mask, thresholds=(2, 4, 8), scale=None):
-    """The depth metrics of a batch (utils.py:125-159) without boolean-mask gathers: est, gt, mask [N,H,W] (mask > 0.5 =
-    valid), scale [N] or None -> (out [1+K] fp32 = abs_depth_error and the error ratio above every threshold, per image
-    then averaged; raw [N,2+K] fp64 = valid pixels, sum of |est*s - gt*s|, errors above every threshold).  Two launches,
-    no synchronisation."""
+def _masked_errors(entry, name, est, gt, mask, thresholds, scale):
     for t, n in ((est, "est"), (gt, "gt"), (mask, "mask"), (scale, "scale")):
-        _chk(t, "depth_metrics:" + n)
+        _chk(t, name + ":" + n)
     if est.dim() != 3 or tuple(gt.shape) != tuple(est.shape) or tuple(mask.shape) != tuple(est.shape):
-        raise RuntimeError("depth_metrics: est, gt and mask must be [N,H,W] tensors of one shape")
+        raise RuntimeError(name + ": est, gt and mask must be [N,H,W] tensors of one shape")
     N, H, W = est.shape
     K = len(thresholds)
     if not 1 <= K <= 8:
-        raise RuntimeError("depth_metrics: 1 to 8 thresholds, got %d" % K)
+        raise RuntimeError("%s: 1 to 8 thresholds, got %d" % (name, K))
     if N <= 0 or H * W <= 0:
-        raise RuntimeError("depth_metrics: empty input %s" % (tuple(est.shape),))
+        raise RuntimeError("%s: empty input %s" % (name, tuple(est.shape)))
     if scale is not None and tuple(scale.shape) != (N,):
-        raise RuntimeError("depth_metrics: scale must hold one value per image")
+        raise RuntimeError(name + ": scale must hold one value per image")
     for t in (gt, mask, scale):
         if t is not None and t.device != est.device:
-            raise RuntimeError("depth_metrics: tensors on different devices")
+            raise RuntimeError(name + ": tensors on different devices")
     lib = _lib.load()
     thres = (ctypes.c_float * K)(*[float(t) for t in thresholds])
     partial = torch.empty(N * lib.mvster_depth_metrics_slots(H * W) * (2 + K), device=est.device, dtype=torch.float64)
     raw = torch.empty(N, 2 + K, device=est.device, dtype=torch.float64)
     out = torch.empty(1 + K, device=est.device, dtype=torch.float32)
-    rc = lib.mvster_depth_metrics(_ptr(est), _ptr(gt), _ptr(mask), _ptr(scale), ctypes.cast(thres, ctypes.c_void_p), K, N, H * W,
-                                  _ptr(partial), _ptr(raw), _ptr(out), _stream())
-    _lib.check(rc, "depth_metrics")
+    rc = getattr(lib, entry)(_ptr(est), _ptr(gt), _ptr(mask), _ptr(scale), ctypes.cast(thres, ctypes.c_void_p), K, N, H * W,
+                             _ptr(partial), _ptr(raw), _ptr(out), _stream())
+    _lib.check(rc, name)
     return out, raw
+
+
+def depth_metrics(est, gt, mask, thresholds=(2, 4, 8), scale=None):
+    """The depth metrics of a batch (utils.py:125-159) without boolean-mask gathers: est, gt, mask [N,H,W] (mask > 0.5 =
+    valid), scale [N] or None -> (out [1+K] fp32 = abs_depth_error and the error ratio above every threshold, per image
+    then averaged; raw [N,2+K] fp64 = valid pixels, sum of |est*s - gt*s|, errors above every threshold).  Two launches,
+    no synchronisation."""
+    return _masked_errors("mvster_depth_metrics", "depth_metrics", est, gt, mask, thresholds, scale)
+
+
+def pooled_metrics(est, gt, mask, thresholds=(3, 1), scale=None):
+    """``Blend_loss``'s error figures (MVS4Net.py:202-205) without a boolean-mask gather, pooled over all valid pixels of
+    the batch: est, gt, mask [N,H,W] (mask > 0.5 = valid), scale [N] or None -> (out [1+K] fp32 = epe, the mean of
+    |est*s - gt*s|, and for every threshold the share of valid pixels with an error at or below it, in per cent; raw
+    [N,2+K] fp64 = per image valid pixels, sum of the errors, errors at or below every threshold).  Two launches, no
+    synchronisation; a batch without a valid pixel gives NaN."""
+    return _masked_errors("mvster_pooled_metrics", "pooled_metrics", est, gt, mask, thresholds, scale)
 
 
 def _chk_meter(sums, count, name):
@@ -1236,6 +1249,26 @@ def scalar_accumulate(row, sums, count):
     if row.dim() != 1 or row.numel() != sums.numel() or row.device != sums.device:
         raise RuntimeError("scalar_accumulate: row must be a [%d] tensor on the device of sums" % sums.numel())
     _lib.check(_lib.load().mvster_scalar_accumulate(_ptr(row), row.numel(), _ptr(sums), _ptr(count), _stream()), "scalar_accumulate")
+
+
+def scalar_gather_accumulate(scalars, row, sums, count):
+    """``torch.stack(scalars)`` into ``row`` and ``scalar_accumulate(row, sums, count)`` in ONE launch: scalars = up to 32
+    one-element fp32 device tensors (views into larger tensors are fine: only their addresses are passed), row [n] fp32.
+    Capturable; the caller keeps the scalars alive."""
+    _chk(row, "scalar_gather_accumulate:row")
+    _chk_meter(sums, count, "scalar_gather_accumulate")
+    n = len(scalars)
+    if not 1 <= n <= 32:
+        raise RuntimeError("scalar_gather_accumulate: 1 to 32 scalars, got %d" % n)
+    if row.dim() != 1 or row.numel() != n or sums.numel() != n or row.device != sums.device:
+        raise RuntimeError("scalar_gather_accumulate: row and sums must be [%d] tensors on one device" % n)
+    for i, t in enumerate(scalars):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 and t.device == row.device):
+            raise RuntimeError("scalar_gather_accumulate: scalar %d is not a one-element fp32 tensor on %s" % (i, row.device))
+    table = (ctypes.c_void_p * n)(*[t.data_ptr() for t in scalars])
+    rc = _lib.load().mvster_scalar_gather_accumulate(ctypes.cast(table, ctypes.c_void_p), n, _ptr(row), _ptr(sums), _ptr(count),
+                                                     _stream())
+    _lib.check(rc, "scalar_gather_accumulate")
 
 
 def scalar_reset(sums, count):

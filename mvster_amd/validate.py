@@ -68,9 +68,10 @@ def validation_scalars(outputs, depth_gt_ms, mask_ms, **loss_kwargs):
         return torch.stack([loss] + list(d_loss) + list(c_loss) + list(range_err) + list(metrics.unbind(0)))
 
 
-def reduce_scalar_sums(sums, count, group=None):
+def reduce_scalar_sums(sums, count, group=None, names=SCALAR_NAMES):
     """The arithmetic of ``Validator.mean``: sums [n] fp64 and count [1] int64 (any device) -> {name: sums[i] / count} as
-    Python floats -- ``DictAverageMeter.mean`` (utils.py:121-122).  With torch.distributed initialised and more than one
+    Python floats -- ``DictAverageMeter.mean`` (utils.py:121-122); ``names``: the n keys (a captured training step over
+    ``Blend_loss`` has 20).  With torch.distributed initialised and more than one
     rank in ``group`` (None: the default group), ONE all-reduce of the fp64 vector ``sums || count`` comes first: every
     rank gets (sum over ranks of sums) / (sum over ranks of count).  The reference averages every sample's scalars over
     the ranks instead (``reduce_scalar_outputs``): with DistributedSampler's equal counts the same mean, summed in
@@ -80,10 +81,11 @@ def reduce_scalar_sums(sums, count, group=None):
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         dist.all_reduce(vec, group=group)
     host = vec.tolist()                      # (the one read-back)
-    if len(host) != len(SCALAR_NAMES) + 1:
-        raise RuntimeError("reduce_scalar_sums: %d sums for the %d names of SCALAR_NAMES" % (len(host) - 1, len(SCALAR_NAMES)))
+    if len(host) != len(names) + 1:
+        raise RuntimeError("reduce_scalar_sums: %d sums for the %d names of %s" % (len(host) - 1, len(names),
+                           "SCALAR_NAMES" if names is SCALAR_NAMES else "names %r" % (tuple(names),)))
     n = host[-1]
-    return {k: (v / n if n else float("nan")) for k, v in zip(SCALAR_NAMES, host[:-1])}
+    return {k: (v / n if n else float("nan")) for k, v in zip(names, host[:-1])}
 
 
 class Validator:
