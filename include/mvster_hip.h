@@ -348,27 +348,22 @@ int mvster_conv_wgrad_finish_batch(const void* recs, int count, void* stream);
  * reference's conv -> BatchNorm -> ReLU blocks (models/mvs4net_utils.py:116-123, :224-251) and its autograd.
  * x [groups*rows, C]: `groups` independent statistics groups of `rows` rows each (the reference normalises every
  * view's batch on its own, MVS4Net.py:65-68); scale = gamma * rstd, shift = beta - mean * scale, mean, rstd are
- * [groups, C] (batch statistics from the caller).
- *   stats:       per-workgroup slots partial[g][n][0][c] / [g][n][1][c] = sum d and sum d^2, d = x - x[first row of g];
- *                a finishing kernel adds the slots in order (fp64) and writes out [5][groups][C] = mean, biased var, rstd,
- *                scale, shift; running_mean / running_var (optional) get the groups' exponential-average updates in
- *                order (momentum, unbiased variance) and num_batches_tracked (optional, device int64) += groups --
- *                what `groups` sequential nn.BatchNorm calls would do
+ * [groups, C] (statistics from the caller: the pack of mvster_bn_train_fwd below, or a module's running statistics).
  *   fwd:         y = relu(x*scale + shift) (+ skip)                      (relu = 0: affine only; skip optional: the U-Net's
  *                same-shape skip connection, added after the activation, models/mvs4net_utils.py:893-895)
- *   bwd_reduce:  slots as above of sum g_ and sum g_*xh; the finishing kernel writes sums [groups][2][C] and the parameter
- *                gradients dbeta [C] = sum_g sum g_, dgamma [C] = sum_g sum g_*xh
+ *   bwd_reduce:  per-workgroup slots partial[g][n][0][c] / [g][n][1][c] = sum g_ and sum g_*xh; the last workgroup to
+ *                arrive writes sums [groups][2][C] and the parameter gradients dbeta [C] = sum_g sum g_, dgamma [C] =
+ *                sum_g sum g_*xh
  *   bwd_apply:   dx = scale * (g_ - sums[g][0]/rows - xh * sums[g][1]/rows),   g_ = gy * (y > 0), xh = (x - mean) * rstd;
  *                frozen = 1 (statistics are constants): dx = scale * g_
- * partial: [groups][mvster_bn_slots(rows, C, groups)][2][C] floats of scratch.  stats and bwd_reduce are ONE launch each:
+ * partial: [groups][mvster_bn_slots(rows, C, groups)][2][C] floats of scratch.  bwd_reduce is ONE launch:
  * the last workgroup to arrive (ticket: one device int, 0 before the call and 0 again after it) adds the slots in a fixed
- * order in fp64 and writes the results (slots published with write-through stores: no L2 write-back); groups*2C <= 2048. */
+ * order in fp64 and writes the results (slots published with write-through stores: no L2 write-back); groups*2C <= 2048.
+ * Training-mode BatchNorm itself is mvster_bn_train_fwd / _bwd below; bwd_reduce + bwd_apply serve the backward of a
+ * BatchNorm in eval mode inside a training graph (frozen = 1). */
 int mvster_bn_relu_fwd(const float* x, const float* scale, const float* shift, const float* skip, float* y, long rows,
                        int C, int relu, int groups, void* stream);
 int mvster_bn_slots(long rows, int C, int groups);
-int mvster_bn_stats(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
-                    long* num_batches_tracked, float* partial, float* out, int* ticket, long rows, int C, int groups,
-                    float eps, float momentum, void* stream);
 int mvster_bn_relu_bwd_reduce(const float* x, const float* gy, const float* scale, const float* shift, const float* mean,
                               const float* rstd, float* partial, float* sums, float* dgamma, float* dbeta, int* ticket,
                               long rows, int C, int relu, int groups, void* stream);
@@ -381,31 +376,23 @@ int mvster_bn_relu_bwd_apply(const float* x, const float* gy, const float* scale
  * monocular heads :846-848).  partial: mvster_bn_slots(rows, C, 1) * 2 * C floats, ticket as above.  One launch. */
 int mvster_col_sum(const float* x, float* partial, float* out, int* ticket, long rows, int C, void* stream);
 
-/* Training-mode BatchNorm as the step runs it since round 6: TWO launches per pass without a serial tail -- the reduction
- * kernel only writes its per-workgroup slots, the apply kernel's workgroups sum them in their prologue (every workgroup its
- * group's, in the same fixed order, fp64), one extra workgroup does the running-average updates (forward) / the parameter
- * gradients (backward).  train_fwd = mvster_bn_stats + mvster_bn_relu_fwd (same `out` pack [5][groups][C], same running
- * updates); train_bwd = mvster_bn_relu_bwd_reduce + _apply (pack = the forward's `out`).  partial: groups *
- * mvster_bn_train_slots(rows, C, groups) * 2 * C floats.  models/mvs4net_utils.py:116-123, :224-251 under autograd. */
+/* Training-mode BatchNorm (+ ReLU, + skip): TWO launches per pass without a serial tail -- the reduction kernel only writes
+ * its per-workgroup slots (forward: sum d and sum d^2, d = x - x[first row of the group]; backward: sum g_ and sum g_*xh),
+ * the apply kernel's workgroups sum them in their prologue (every workgroup its group's, in the same fixed order, fp64), one
+ * extra workgroup does the running-average updates (forward) / the parameter gradients (backward).
+ *   train_fwd:  y = relu(x*scale + shift) (+ skip) with batch statistics; out [5][groups][C] = mean, biased var, rstd,
+ *               scale, shift; running_mean / running_var (optional) get the groups' exponential-average updates in order
+ *               (momentum, unbiased variance) and num_batches_tracked (optional, device int64) += groups -- what `groups`
+ *               sequential nn.BatchNorm calls would do
+ *   train_bwd:  dx as bwd_apply above with frozen = 0, dgamma / dbeta [C] summed over the groups; pack = the forward's `out`
+ * partial: groups * mvster_bn_train_slots(rows, C, groups) * 2 * C floats; groups*2C <= 2048.
+ * models/mvs4net_utils.py:116-123, :224-251 under autograd. */
 int mvster_bn_train_slots(long rows, int C, int groups);
 int mvster_bn_train_fwd(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
                         long* num_batches_tracked, const float* skip, float* partial, float* y, float* out, long rows, int C,
                         int relu, int groups, float eps, float momentum, void* stream);
 int mvster_bn_train_bwd(const float* x, const float* gy, const float* pack, float* partial, float* dgamma, float* dbeta, float* dx,
                         long rows, int C, int relu, int groups, void* stream);
-
-/* The same BatchNorm passes for SMALL tensors in one launch each way (most layers of the step: coarse stages, deep U-Net
- * levels): a thread keeps its <= 8 (backward: 4) float4 of x (and gy) in registers across the reduction, the last workgroup
- * to arrive finishes and publishes the statistics and releases the others, which spin on a flag -- a grid barrier among at
- * most 128 resident workgroups.  fwd_fused = mvster_bn_stats + mvster_bn_relu_fwd (same `out`, same running updates);
- * bwd_fused = mvster_bn_relu_bwd_reduce + _apply (pack = the forward's `out`).  partial: groups * 128 * 2 * C floats; sync: 3
- * device ints, zero before and after.  mvster_bn_fused_ok(rows, C, groups, backward) says whether a tensor fits (16 / 8 MB). */
-int mvster_bn_fused_ok(long rows, int C, int groups, int backward);
-int mvster_bn_fwd_fused(const float* x, const float* skip, float* y, const float* weight, const float* bias, float* running_mean,
-                        float* running_var, long* num_batches_tracked, float* partial, float* out, int* sync, long rows, int C,
-                        int relu, int groups, float eps, float momentum, void* stream);
-int mvster_bn_bwd_fused(const float* x, const float* gy, const float* pack, float* partial, float* sums, float* dgamma,
-                        float* dbeta, float* dx, int* sync, long rows, int C, int relu, int groups, void* stream);
 
 /* Bilinear x2 up-sampling (align_corners=True) of a channels-last map, in [B,h,w,C] -> out [B,2h,2w,C], and its
  * adjoint gout [B,2h,2w,C] -> gin [B,h,w,C] as a gather (no atomics): the FPN top-down path in training

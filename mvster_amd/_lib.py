@@ -63,11 +63,7 @@ SIGNATURES = {
     "mvster_bn_train_slots": [_l, _i, _i],
     "mvster_bn_train_fwd": [_f] * 10 + [_l, _i, _i, _i, _fl, _fl, _f],
     "mvster_bn_train_bwd": [_f] * 7 + [_l, _i, _i, _i, _f],
-    "mvster_bn_fused_ok": [_l, _i, _i, _i],
-    "mvster_bn_fwd_fused": [_f] * 11 + [_l, _i, _i, _i, _fl, _fl, _f],
-    "mvster_bn_bwd_fused": [_f] * 9 + [_l, _i, _i, _i, _f],
     "mvster_conv_wgrad_finish_batch": [_f, _i, _f],
-    "mvster_bn_stats": [_f] * 9 + [_l, _i, _i, _fl, _fl, _f],
     "mvster_bn_relu_bwd_reduce": [_f] * 11 + [_l, _i, _i, _i, _f],
     "mvster_bn_relu_bwd_apply": [_f] * 8 + [_l, _i, _i, _i, _i, _f],
     "mvster_upsample2x_cl_fwd": [_f, _f, _i, _i, _i, _i, _f],

@@ -819,9 +819,10 @@ _TICKETS = {}
 
 
 def _ticket(dev):
-    """Address of four zero int32s on ``dev`` for a one-launch reduction's arrival counter / a fused pass's grid barrier
-    (the kernels leave them at zero).  Handed out round-robin from a pool: launches that could overlap (other streams)
-    practically never share one."""
+    """Address of four zero int32s on ``dev`` for the arrival counter of a one-launch reduction (``col_sum``,
+    ``bn_relu_bwd``): the last workgroup to arrive finishes the sum and leaves the counter at zero.  Nothing waits on a
+    ticket.  Handed out round-robin from a pool of 4096, so that launches which could overlap (other streams) do not share
+    one; two that did would each miscount their arrivals (a wrong sum, not a hang)."""
     hit = _TICKETS.get(dev)
     if hit is None:
         hit = _TICKETS[dev] = [torch.zeros(4 * 4096, device=dev, dtype=torch.int32), 0]
@@ -829,40 +830,28 @@ def _ticket(dev):
     return hit[0].data_ptr() + 16 * hit[1]
 
 
-_BN_FUSED_OK = {}
-# Small tensors: BatchNorm statistics + apply (reduce + apply) in ONE launch with a resident-grid barrier.  OFF: measured on
-# the config-4 step it takes 62 launches away (216 -> 154) and saves nothing -- 12.92 against 12.88 ms: the barrier is ~6
-# dependent memory round trips (slot drain, ticket, slot loads, statistics publish, flag poll, statistics loads), 13 us
-# for a tensor the two launches handle in 10 + 5 (profiles/r06_*bn_fused_ab.txt).  Kept behind this switch with its tests.
-BN_FUSED = False
-
-
-def bn_fused_ok(rows, C, groups, backward):
-    key = (rows, C, groups, backward)
-    ok = _BN_FUSED_OK.get(key)
-    if ok is None:
-        ok = _BN_FUSED_OK[key] = bool(_lib.load().mvster_bn_fused_ok(rows, C, groups, int(backward)))
-    return ok and BN_FUSED
-
-
-BN_TAILLESS = True            # training BatchNorm: slot sums in the apply kernels' prologue (False: last-arriver reductions)
+def _bn_train_args(name, x, groups, *others):
+    """The checks ``bn_train_fwd`` and ``bn_train_bwd`` share -> (C, rows per group, a fresh slot buffer)."""
+    _chk(x, name + ":x")
+    for t, n in others:
+        _chk(t, "%s:%s" % (name, n))
+    C = x.shape[-1]
+    rows = x.numel() // C // groups
+    nblk = _bn_train_slots(rows, C, groups)
+    if nblk <= 0:
+        raise RuntimeError("%s: unsupported channel count %d" % (name, C))
+    return C, rows, torch.empty(groups, nblk, 2, C, device=x.device, dtype=torch.float32)
 
 
 def bn_train_fwd(x, weight, bias, running_mean, running_var, eps, momentum, relu, groups=1, num_batches_tracked=None, skip=None):
-    """Training-mode BatchNorm (+ ReLU, + skip): slots, then apply with the statistics finished in its prologue -> (y, pack);
-    the running statistics / counter are updated in place like ``bn_batch_stats``."""
-    _chk(x, "bn_train_fwd:x")
-    _chk(skip, "bn_train_fwd:skip")
-    C = x.shape[-1]
-    rows = x.numel() // C // groups
+    """Training-mode BatchNorm (+ ReLU, + skip): slots, then apply with the statistics finished in its prologue -> (y, pack),
+    pack [5, groups, C] = (mean, biased var, rstd, scale, shift); running_mean / running_var (or None) are updated in
+    place, one exponential-average step per group, and num_batches_tracked (or None) += groups."""
+    C, rows, partial = _bn_train_args("bn_train_fwd", x, groups, (skip, "skip"))
     if skip is not None and tuple(skip.shape) != tuple(x.shape):
         raise RuntimeError("bn_train_fwd: skip must have the shape of x")
     if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
         raise RuntimeError("bn_train_fwd: num_batches_tracked must be an int64 tensor on the device")
-    nblk = _bn_train_slots(rows, C, groups)
-    if nblk <= 0:
-        raise RuntimeError("bn_train_fwd: unsupported channel count %d" % C)
-    partial = torch.empty(groups, nblk, 2, C, device=x.device, dtype=torch.float32)
     pack = torch.empty(5, groups, C, device=x.device, dtype=torch.float32)
     y = torch.empty_like(x)
     rc = _lib.load().mvster_bn_train_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var),
@@ -874,79 +863,13 @@ def bn_train_fwd(x, weight, bias, running_mean, running_var, eps, momentum, relu
 
 def bn_train_bwd(x, gy, pack, relu, groups=1):
     """Backward of ``bn_train_fwd`` -> (dx, dbeta, dgamma): slots, then dx with the sums formed in its prologue."""
-    _chk(x, "bn_train_bwd:x")
-    _chk(gy, "bn_train_bwd:gy")
-    _chk(pack, "bn_train_bwd:pack")
-    C = x.shape[-1]
-    rows = x.numel() // C // groups
-    nblk = _bn_train_slots(rows, C, groups)
-    if nblk <= 0:
-        raise RuntimeError("bn_train_bwd: unsupported channel count %d" % C)
-    partial = torch.empty(groups, nblk, 2, C, device=x.device, dtype=torch.float32)
+    C, rows, partial = _bn_train_args("bn_train_bwd", x, groups, (gy, "gy"), (pack, "pack"))
     dgb = torch.empty(2, C, device=x.device, dtype=torch.float32)
     dx = torch.empty_like(x)
     rc = _lib.load().mvster_bn_train_bwd(_ptr(x), _ptr(gy), _ptr(pack), _ptr(partial), _ptr(dgb[0]), _ptr(dgb[1]), _ptr(dx), rows,
                                          C, int(relu), int(groups), _stream())
     _lib.check(rc, "bn_train_bwd")
     return dx, dgb[1], dgb[0]
-
-
-def bn_fwd_fused(x, weight, bias, running_mean, running_var, eps, momentum, relu, groups=1, num_batches_tracked=None, skip=None):
-    """``bn_batch_stats`` + ``bn_relu_fwd`` of a small tensor in ONE launch -> (y, pack)."""
-    _chk(x, "bn_fwd_fused:x")
-    _chk(skip, "bn_fwd_fused:skip")
-    C = x.shape[-1]
-    rows = x.numel() // C // groups
-    if skip is not None and tuple(skip.shape) != tuple(x.shape):
-        raise RuntimeError("bn_fwd_fused: skip must have the shape of x")
-    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
-        raise RuntimeError("bn_fwd_fused: num_batches_tracked must be an int64 tensor on the device")
-    partial = torch.empty(groups, 128, 2, C, device=x.device, dtype=torch.float32)
-    pack = torch.empty(5, groups, C, device=x.device, dtype=torch.float32)
-    y = torch.empty_like(x)
-    rc = _lib.load().mvster_bn_fwd_fused(_ptr(x), _ptr(skip), _ptr(y), _ptr(weight), _ptr(bias), _ptr(running_mean),
-                                         _ptr(running_var), _ptr(num_batches_tracked), _ptr(partial), _ptr(pack),
-                                         _ticket(x.device), rows, C, int(relu), int(groups), float(eps), float(momentum), _stream())
-    _lib.check(rc, "bn_fwd_fused")
-    return y, pack
-
-
-def bn_bwd_fused(x, gy, pack, relu, groups=1):
-    """``bn_relu_bwd`` of a small tensor in ONE launch -> (dx, dbeta, dgamma)."""
-    _chk(x, "bn_bwd_fused:x")
-    _chk(gy, "bn_bwd_fused:gy")
-    _chk(pack, "bn_bwd_fused:pack")
-    C = x.shape[-1]
-    rows = x.numel() // C // groups
-    partial = torch.empty(groups, 128, 2, C, device=x.device, dtype=torch.float32)
-    sums = torch.empty(groups, 2, C, device=x.device, dtype=torch.float32)
-    dgb = torch.empty(2, C, device=x.device, dtype=torch.float32)
-    dx = torch.empty_like(x)
-    rc = _lib.load().mvster_bn_bwd_fused(_ptr(x), _ptr(gy), _ptr(pack), _ptr(partial), _ptr(sums), _ptr(dgb[0]), _ptr(dgb[1]),
-                                         _ptr(dx), _ticket(x.device), rows, C, int(relu), int(groups), _stream())
-    _lib.check(rc, "bn_bwd_fused")
-    return dx, dgb[1], dgb[0]
-
-
-def bn_batch_stats(x, weight, bias, running_mean, running_var, eps, momentum, groups=1, num_batches_tracked=None):
-    """-> pack [5, groups, C] = (mean, biased var, rstd, scale, shift); running_mean / running_var (or None) are
-    updated in place, one exponential-average step per group, and num_batches_tracked (or None) += groups."""
-    _chk(x, "bn_batch_stats:x")
-    C = x.shape[-1]
-    rows = x.numel() // C // groups
-    lib = _lib.load()
-    nblk = _bn_slots(rows, C, groups)
-    if nblk <= 0:
-        raise RuntimeError("bn_batch_stats: unsupported channel count %d" % C)
-    partial = torch.empty(groups, nblk, 2, C, device=x.device, dtype=torch.float32)
-    pack = torch.empty(5, groups, C, device=x.device, dtype=torch.float32)
-    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
-        raise RuntimeError("bn_batch_stats: num_batches_tracked must be an int64 tensor on the device")
-    rc = lib.mvster_bn_stats(_ptr(x), _ptr(weight), _ptr(bias), _ptr(running_mean), _ptr(running_var),
-                             _ptr(num_batches_tracked), _ptr(partial), _ptr(pack), _ticket(x.device), rows, C, int(groups),
-                             float(eps), float(momentum), _stream())
-    _lib.check(rc, "bn_stats")
-    return pack
 
 
 def bn_relu_fwd(x, scale, shift, relu, groups=1, skip=None):
@@ -967,10 +890,11 @@ def bn_relu_fwd(x, scale, shift, relu, groups=1, skip=None):
     return y
 
 
-def bn_relu_bwd(x, gy, scale, shift, mean, rstd, relu, groups=1, frozen=False):
-    """-> (dx, dbeta [C] = sum g, dgamma [C] = sum g*xh) with g = gy*(y>0), xh = (x-mean)*rstd (BatchNorm + ReLU backward,
-    batch statistics per group; the parameter gradients are summed over the groups).  ``frozen``: mean /
-    rstd are constants (running statistics), so dx = g * scale."""
+def bn_relu_bwd(x, gy, scale, shift, mean, rstd, relu, groups=1):
+    """Backward of ``bn_relu_fwd``, whose scale / shift / mean / rstd are constants (a BatchNorm in eval mode inside a
+    training graph: the running statistics) -> (dx = g * scale, dbeta [C] = sum g, dgamma [C] = sum g*xh) with g =
+    gy*(y>0), xh = (x-mean)*rstd; the parameter gradients are summed over the groups.  The backward through batch
+    statistics is ``bn_train_bwd``."""
     _chk(x, "bn_relu_bwd:x")
     _chk(gy, "bn_relu_bwd:gy")
     C = x.shape[-1]
@@ -988,7 +912,7 @@ def bn_relu_bwd(x, gy, scale, shift, mean, rstd, relu, groups=1, frozen=False):
     _lib.check(rc, "bn_relu_bwd_reduce")
     dx = torch.empty_like(x)
     rc = lib.mvster_bn_relu_bwd_apply(_ptr(x), _ptr(gy), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(sums),
-                                      _ptr(dx), rows, C, int(relu), int(groups), int(frozen), _stream())
+                                      _ptr(dx), rows, C, int(relu), int(groups), 1, _stream())          # (frozen = 1)
     _lib.check(rc, "bn_relu_bwd_apply")
     return dx, dgb[1], dgb[0]
 

@@ -100,7 +100,7 @@ class _LayerCache:
         self._d = {}
         self.cells = _EpochCells()     # parameter / buffer -> [epoch]; see above
         self.always_repack = False
-        # bumped whenever a training-mode BatchNorm writes running statistics through raw pointers (ops.bn_batch_stats moves
+        # bumped whenever a training-mode BatchNorm writes running statistics through raw pointers (ops.bn_train_fwd moves
         # no ``_version``): part of ``MVS4net._state_stamp``, so an eval graph folded from the old statistics is not replayed
         self.stat_writes = 0
         self._batch = None             # see build_batch()
@@ -456,52 +456,46 @@ def fpn_fine_level(c_low, f_coarse, inner, out):
     return conv_cl(c_low, wc, out.bias, out.stride, out.padding, skip=P, owner=(out.weight, "_fine_c"))
 
 
-class _BnReluCL(torch.autograd.Function):
-    """relu(BatchNorm(x)) given the statistics pack [5, groups, C] = (mean, var, rstd, scale, shift): fused apply kernel
-    forward, two fused kernels backward.  ``frozen``: the pack holds the running statistics (a BatchNorm in eval mode
-    inside a training graph), which do not depend on x."""
+class _BnTrainCL(torch.autograd.Function):
+    """relu(BatchNorm(x)) (+ skip) on batch statistics: ``ops.bn_train_fwd`` (statistics slots, then the apply kernel sums
+    them in its prologue and updates the running statistics) and ``ops.bn_train_bwd``, two launches each way."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, pack, relu, groups, frozen, skip=None):
+    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, eps, momentum, relu, groups, skip=None):
+        y, pack = ops.bn_train_fwd(x, weight.detach(), bias.detach(), running_mean, running_var, eps, momentum, relu, groups,
+                                   num_batches_tracked=nbt, skip=None if skip is None else skip.contiguous())
         ctx.save_for_backward(x, pack)
-        ctx.cfg = (relu, groups, frozen, skip is not None)
+        ctx.cfg = (relu, groups, skip is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, pack = ctx.saved_tensors
+        relu, groups, has_skip = ctx.cfg
+        gy = gy.contiguous()
+        dx, dbeta, dgamma = ops.bn_train_bwd(x, gy, pack, relu, groups)
+        gskip = gy if has_skip else None          # the skip connection's gradient is the output gradient itself
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None, gskip
+
+
+class _BnFrozenCL(torch.autograd.Function):
+    """relu(BatchNorm(x)) (+ skip) of a BatchNorm in eval mode inside a training graph: the pack [5, groups, C] = (mean, var,
+    rstd, scale, shift) holds the running statistics, which do not depend on x."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pack, relu, groups, skip=None):
+        ctx.save_for_backward(x, pack)
+        ctx.cfg = (relu, groups, skip is not None)
         return ops.bn_relu_fwd(x, pack[3], pack[4], relu, groups, skip=None if skip is None else skip.contiguous())
 
     @staticmethod
     def backward(ctx, gy):
         x, pack = ctx.saved_tensors
-        relu, groups, frozen, has_skip = ctx.cfg
+        relu, groups, has_skip = ctx.cfg
         gy = gy.contiguous()
-        C = x.shape[-1]
-        if not frozen and ops.bn_fused_ok(x.numel() // C // groups, C, groups, True):
-            dx, dbeta, dgamma = ops.bn_bwd_fused(x, gy, pack, relu, groups)          # (small tensor: one launch)
-        elif not frozen and ops.BN_TAILLESS:
-            dx, dbeta, dgamma = ops.bn_train_bwd(x, gy, pack, relu, groups)          # (slot sums in the apply kernel's prologue)
-        else:
-            dx, dbeta, dgamma = ops.bn_relu_bwd(x, gy, pack[3], pack[4], pack[0], pack[2], relu, groups, frozen)
+        dx, dbeta, dgamma = ops.bn_relu_bwd(x, gy, pack[3], pack[4], pack[0], pack[2], relu, groups)
         gskip = gy if has_skip else None          # the skip connection's gradient is the output gradient itself
-        return dx, dgamma, dbeta, None, None, None, None, gskip
-
-
-class _BnFusedCL(torch.autograd.Function):
-    """Training-mode relu(BatchNorm(x)) (+ skip) with the statistics finished INSIDE the forward op: ``mvster_bn_train_fwd``
-    (slots, then the apply kernel sums them in its prologue) or, behind ``ops.BN_FUSED``, ``mvster_bn_fwd_fused`` (a small
-    tensor in one launch); the backward is ``_BnReluCL``'s, which picks the matching form."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, nbt, eps, momentum, relu, groups, skip=None):
-        C = x.shape[-1]
-        fn = ops.bn_fwd_fused if ops.bn_fused_ok(x.numel() // C // groups, C, groups, False) else ops.bn_train_fwd
-        y, pack = fn(x, weight.detach(), bias.detach(), running_mean, running_var, eps, momentum, relu, groups,
-                     num_batches_tracked=nbt, skip=None if skip is None else skip.contiguous())
-        ctx.save_for_backward(x, pack)
-        ctx.cfg = (relu, groups, False, skip is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        dx, dgamma, dbeta, _, _, _, _, gskip = _BnReluCL.backward(ctx, gy)
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, gskip
+        return dx, dgamma, dbeta, None, None, None, gskip
 
 
 def batch_norm_cl(x, bn, relu=False, groups=1, skip=None):
@@ -527,21 +521,14 @@ def batch_norm_cl(x, bn, relu=False, groups=1, skip=None):
             raise NotImplementedError("batch_norm_cl: cumulative-average running statistics (momentum=None)")
         if track:
             CACHE.stat_writes += 1
-        if ops.BN_TAILLESS or ops.bn_fused_ok(x.numel() // C // groups, C, groups, False):
-            # statistics slots + apply with the finish in its prologue (or, behind ops.BN_FUSED, a small tensor in ONE launch)
-            return _BnFusedCL.apply(x, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
-                                    bn.num_batches_tracked if track else None, bn.eps, bn.momentum or 0.0, relu, groups, skip)
-        with torch.no_grad():
-            pack = ops.bn_batch_stats(x, bn.weight, bn.bias, bn.running_mean if track else None,
-                                      bn.running_var if track else None, bn.eps, bn.momentum or 0.0, groups,
-                                      num_batches_tracked=bn.num_batches_tracked if track else None)
-        return _BnReluCL.apply(x, bn.weight, bn.bias, pack, relu, groups, False, skip)
+        return _BnTrainCL.apply(x, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
+                                bn.num_batches_tracked if track else None, bn.eps, bn.momentum or 0.0, relu, groups, skip)
     with torch.no_grad():            # [C]-sized parameter preparation, like weight packing
         rstd = torch.rsqrt(bn.running_var + bn.eps)
         scale = bn.weight * rstd
         pack = torch.stack([bn.running_mean, bn.running_var, rstd, scale, bn.bias - bn.running_mean * scale])
         pack = pack.unsqueeze(1).expand(5, groups, C).contiguous()
-    return _BnReluCL.apply(x, bn.weight, bn.bias, pack, relu, groups, True, skip)
+    return _BnFrozenCL.apply(x, bn.weight, bn.bias, pack, relu, groups, skip)
 
 
 class _Upsample2xCL(torch.autograd.Function):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""BatchNorm kernels in isolation at the training step's shapes: achieved GB/s of the four passes (stats, apply, backward
-reduce, backward apply) -- algorithmic bytes = reads + writes of the tensor(s)."""
+"""Training-mode BatchNorm in isolation at the training step's shapes, as the step runs it: achieved GB/s of the forward
+(ops.bn_train_fwd: statistics slots + apply) and the backward (ops.bn_train_bwd: slots + apply) -- algorithmic bytes = reads
++ writes of the tensor(s): 3 passes forward (x twice, y), 5 backward (x and gy twice, dx)."""
 import os
 import sys
 
@@ -35,10 +36,9 @@ for shape, groups in shapes:
     w, b = torch.ones(C, device=dev), torch.zeros(C, device=dev)
     rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
     nbt = torch.zeros((), dtype=torch.int64, device=dev)
-    pack = ops.bn_batch_stats(x, w, b, rm, rv, 1e-5, 0.1, groups, num_batches_tracked=nbt)
+    y, pack = ops.bn_train_fwd(x, w, b, rm, rv, 1e-5, 0.1, True, groups, num_batches_tracked=nbt)
     mb = x.numel() * 4 / 1e6
-    t_stats = timeit(lambda: ops.bn_batch_stats(x, w, b, rm, rv, 1e-5, 0.1, groups, num_batches_tracked=nbt))
-    t_fwd = timeit(lambda: ops.bn_relu_fwd(x, pack[3], pack[4], True, groups))
-    t_bwd = timeit(lambda: ops.bn_relu_bwd(x, gy, pack[3], pack[4], pack[0], pack[2], True, groups))
-    print("%-24s g=%d %7.1f MB  stats %6.1f us %5.0f GB/s   apply %6.1f us %5.0f GB/s   bwd (reduce+apply) %6.1f us %5.0f GB/s"
-          % (shape, groups, mb, t_stats, mb / t_stats * 1e3, t_fwd, 2 * mb / t_fwd * 1e3, t_bwd, 5 * mb / t_bwd * 1e3), flush=True)
+    t_fwd = timeit(lambda: ops.bn_train_fwd(x, w, b, rm, rv, 1e-5, 0.1, True, groups, num_batches_tracked=nbt))
+    t_bwd = timeit(lambda: ops.bn_train_bwd(x, gy, pack, True, groups))
+    print("%-24s g=%d %7.1f MB  fwd (slots+apply) %6.1f us %5.0f GB/s   bwd (slots+apply) %6.1f us %5.0f GB/s"
+          % (shape, groups, mb, t_fwd, 3 * mb / t_fwd * 1e3, t_bwd, 5 * mb / t_bwd * 1e3), flush=True)

@@ -32,6 +32,18 @@ def test_every_declared_symbol_is_exported(lib):
     assert sorted(_lib.SIGNATURES.keys()) == names
 
 
+def test_retired_batch_norm_forms_are_gone(lib):
+    """Training-mode BatchNorm has one path (mvster_bn_train_fwd / _bwd).  The last-arriver statistics kernel and the
+    grid-barrier small-tensor form are neither bound, exported nor declared, and ops has
+    no switch or wrapper for them."""
+    from mvster_amd import _lib, ops
+    header = open(os.path.join(ROOT, "include", "mvster_hip.h")).read()
+    for name in ("mvster_bn_stats", "mvster_bn_fused_ok", "mvster_bn_fwd_fused", "mvster_bn_bwd_fused"):
+        assert name not in _lib.SIGNATURES and not hasattr(lib, name) and name not in header, name
+    for name in ("BN_FUSED", "BN_TAILLESS", "bn_fused_ok", "bn_fwd_fused", "bn_bwd_fused", "bn_batch_stats"):
+        assert not hasattr(ops, name), name
+
+
 def test_last_kernel_accessor(lib):
     from mvster_amd import _lib
     assert _lib.last_kernel() == ""            # nothing launched in this process (no GPU here)

@@ -1535,36 +1535,48 @@ def test_fused_adam_null_gradient_changes_nothing():
 @pytest.mark.parametrize("shape,groups,relu,with_skip", [((2, 8, 8, 10, 64), 1, True, True), ((2, 4, 64, 80, 16), 1, True, False),
                                                          ((10, 1, 64, 80, 64), 5, True, False), ((6, 1, 100, 128, 16), 3, False, True),
                                                          ((2, 8, 64, 80, 8), 1, True, False)])
-def test_batch_norm_cl_fused_small_tensor_form(monkeypatch, shape, groups, relu, with_skip):
-    """ops.BN_FUSED (off by default: measured no faster): statistics + apply and reduce + apply of a small tensor in one launch
-    each with a resident-grid barrier -- the same output, running statistics and gradients as the two-launch forms (the
-    reductions are summed in another order: agreement to rounding), and the barrier's counters are left at zero."""
+def test_batch_norm_cl_small_tensors_vs_fp64(shape, groups, relu, with_skip):
+    """The small-tensor regime of the training step (coarse cascade stages, deep U-Net levels: 0.3-13 MB, one to a few
+    slots per group) against fp64 ``torch.nn.BatchNorm3d`` on the CPU, ``groups`` sequential module calls per forward: two
+    forwards, then one backward through the second.  Output and running statistics to 2e-6, the three gradients to 2e-5, of
+    max|reference|; the counter; the skip gradient is the output gradient itself; the ticket pool is left at zero.  Measured over the five cases
+    (MI355X): y <= 1.3e-7, running statistics <= 4.7e-7, gradients <= 1.8e-7; torch's own fp32 BatchNorm3d on the same device
+    against the same reference: 1.7e-7, 3.0e-7, 2.5e-7."""
     C = shape[-1]
     g = torch.Generator().manual_seed(C + groups)
-    x0 = (torch.randn(shape, generator=g) * 2 + 0.5).to(DEV)
-    skip0 = torch.randn(shape, generator=g).to(DEV) if with_skip else None
-    gout = torch.randn(shape, generator=g).to(DEV)
-    res = []
-    for fused in (False, True):
-        monkeypatch.setattr(ops, "BN_FUSED", fused)
-        bn = (torch.nn.BatchNorm3d(C) if shape[1] > 1 else torch.nn.BatchNorm3d(C)).to(DEV).train()
+    x0 = torch.randn(shape, generator=g) * 2 + 0.5
+    skip0 = torch.randn(shape, generator=g) if with_skip else None
+    gout = torch.randn(shape, generator=g)
+    ref, bn = torch.nn.BatchNorm3d(C).double(), torch.nn.BatchNorm3d(C).to(DEV).train()
+    for m in (ref, bn):
         with torch.no_grad():
-            bn.weight.copy_(torch.linspace(0.5, 1.5, C))
-            bn.bias.copy_(torch.linspace(-0.2, 0.2, C))
-        x = x0.clone().requires_grad_(True)
-        sk = skip0.clone().requires_grad_(True) if with_skip else None
-        for _ in range(2):                                   # twice: the barrier's counters must come back to zero
-            y = T.batch_norm_cl(x, bn, relu=relu, groups=groups, skip=sk)
-        (y * gout).sum().backward()
-        res.append((y.detach(), x.grad, bn.weight.grad, bn.bias.grad, bn.running_mean.clone(), bn.running_var.clone(),
-                    int(bn.num_batches_tracked), None if sk is None else sk.grad))
-    a, b = res
-    assert a[6] == b[6] == 2 * groups
-    for i, tol in ((0, 2e-6), (1, 2e-5), (2, 2e-5), (3, 2e-5), (4, 2e-6), (5, 2e-6)):
-        scale = a[i].abs().max().item() + 1e-30
-        assert (a[i] - b[i]).abs().max().item() <= tol * scale, (i, (a[i] - b[i]).abs().max().item(), scale)
+            m.weight.copy_(torch.linspace(0.5, 1.5, C))
+            m.bias.copy_(torch.linspace(-0.2, 0.2, C))
+    per = shape[0] // groups
+    xa = x0.double().permute(0, 4, 1, 2, 3).contiguous().requires_grad_(True)
+    for _ in range(2):
+        ya = torch.cat([ref(xa[v * per:(v + 1) * per]) for v in range(groups)], 0)
+        ya = torch.relu(ya) if relu else ya
+    ya.backward(gout.double().permute(0, 4, 1, 2, 3))
+    ya = ya.detach().permute(0, 2, 3, 4, 1)
     if with_skip:
-        assert torch.equal(a[7], b[7])
+        ya = ya + skip0.double()
+    x = x0.to(DEV).requires_grad_(True)
+    sk = skip0.to(DEV).requires_grad_(True) if with_skip else None
+    gdev = gout.to(DEV)
+    for _ in range(2):
+        y = T.batch_norm_cl(x, bn, relu=relu, groups=groups, skip=sk)
+    y.backward(gdev)
+    pairs = {"y": (y.detach(), ya, 2e-6), "dx": (x.grad, xa.grad.permute(0, 2, 3, 4, 1), 2e-5),
+             "dgamma": (bn.weight.grad, ref.weight.grad, 2e-5), "dbeta": (bn.bias.grad, ref.bias.grad, 2e-5),
+             "running_mean": (bn.running_mean, ref.running_mean, 2e-6), "running_var": (bn.running_var, ref.running_var, 2e-6)}
+    ratio = {k: ((got.cpu().double() - want).abs().max() / want.abs().max()).item() for k, (got, want, _) in pairs.items()}
+    note("bn_small_%s_g%d" % ("x".join(map(str, shape)), groups), **ratio)
+    for k, (_, _, tol) in pairs.items():
+        assert ratio[k] <= tol, (k, ratio[k])
+    assert int(bn.num_batches_tracked) == int(ref.num_batches_tracked) == 2 * groups
+    if with_skip:
+        assert torch.equal(sk.grad, gdev)
     tk = ops._TICKETS[DEV][0] if DEV in ops._TICKETS else None
     torch.cuda.synchronize()
     assert tk is None or int(tk.abs().sum()) == 0
