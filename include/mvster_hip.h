@@ -99,6 +99,23 @@ int mvster_warp_agg_fwd_indexed(const float* store, const int* views, const floa
                                 float* wsum_out, int V, int B, int NV, int C, int G, int D, int h, int w, int group_cor,
                                 int attn_fuse_d, float attn_temp, int variant, void* stream);
 
+/* mvster_warp_agg_fwd / mvster_warp_agg_fwd_indexed with a source count per batch item: `nsrc` is a DEVICE int32 array [B]
+ * and item b aggregates its first nsrc[b] sources, 1 <= nsrc[b] <= NV (NOT checked on the device: the caller validates the
+ * counts before uploading them).  NV stays the capacity: rt is [B,NV,12] and the table [B,1+NV] with the same strides, and
+ * nothing of the slots v >= nsrc[b] is read -- neither their rt rows, nor their table entries, nor their maps.  One captured
+ * graph therefore serves reference views with any number of sources up to NV.  Same kernels and combinations as the
+ * uncounted entries (the count is the bound of their view loop, one scalar load per workgroup); with count n the bits of the
+ * uncounted entry called with NV = n on the first n sources.  MVSTER_ERR_NULL (-1) also for nsrc == NULL;
+ * MVSTER_ERR_UNSUPPORTED (-3) where the uncounted entries return it. */
+int mvster_warp_agg_fwd_counted(const float* ref_feat, const float* src_feat, const float* rt, const float* hypo,
+                                float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w, int Hs,
+                                int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride, int group_cor,
+                                int attn_fuse_d, float attn_temp, int variant, const int* nsrc, void* stream);
+int mvster_warp_agg_fwd_indexed_counted(const float* store, const int* views, const float* rt, const float* hypo, float* out,
+                                        float* wsum_out, int V, int B, int NV, int C, int G, int D, int h, int w,
+                                        int group_cor, int attn_fuse_d, float attn_temp, int variant, const int* nsrc,
+                                        void* stream);
+
 /* Maps views[b][k] (DEVICE int32 table [B,N], unchecked) of a level store [V, map_floats] -> out [N,B,map_floats]: the
  * view-major batch mvster_warp_agg_fwd reads (ref_feat = out, src_feat = out + B*map_floats).  map_floats % 4 == 0. */
 int mvster_gather_views(const float* store, const int* views, float* out, int V, int B, int N, long map_floats, void* stream);

@@ -26,6 +26,8 @@ SIGNATURES = {
     "mvster_forward_prologue": [_f, _i, _f, _i, _i, _i, _f, _i, _f, _f, _i, _f, _i, _i, _i, _i, _f],
     "mvster_warp_agg_fwd": [_f, _f, _f, _f, _f, _f] + [_i] * 9 + [_l] * 3 + [_i, _i, _fl, _i, _f],
     "mvster_warp_agg_fwd_indexed": [_f, _f, _f, _f, _f, _f] + [_i] * 10 + [_fl, _i, _f],
+    "mvster_warp_agg_fwd_counted": [_f, _f, _f, _f, _f, _f] + [_i] * 9 + [_l] * 3 + [_i, _i, _fl, _i, _f, _f],
+    "mvster_warp_agg_fwd_indexed_counted": [_f, _f, _f, _f, _f, _f] + [_i] * 10 + [_fl, _i, _f, _f],
     "mvster_gather_views": [_f, _f, _f, _i, _i, _i, _l, _f],
     "mvster_warp_agg_fwd_sched": [_f] * 6 + [_i, _f, _f, _f] + [_i] * 9 + [_l] * 3 + [_i, _fl, _i, _f],
     "mvster_warp_agg_bwd": [_f] * 11 + [_i] * 9 + [_l] * 3 + [_i, _i, _fl, _f],

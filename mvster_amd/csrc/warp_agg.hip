@@ -56,6 +56,9 @@ struct WarpAggArgs {
     // batch item b reads maps views[b * (1 + NV) + 0] (reference) and [.. + 1 + v] (source v) of it
     const int* views;        // DEVICE table [B, 1 + NV]; nullptr in the plain forms
     long store_vs;           // view stride of the store (elements)
+    // counted forms (mvster_warp_agg_fwd_counted / _indexed_counted): batch item b aggregates its first nsrc[b] sources; NV
+    // stays the capacity (the strides of rt and of the table), and nothing of the slots v >= nsrc[b] is read
+    const int* nsrc = nullptr;   // DEVICE [B], 1 <= nsrc[b] <= NV; nullptr: every item uses all NV sources
 };
 
 // Base address of a view's map: the ONLY difference between the plain and the indexed launch forms.  The table entry is
@@ -70,6 +73,9 @@ __device__ __forceinline__ const float* src_base(const WarpAggArgs& a, int b, in
     if constexpr (IDX) return a.src + (long)a.views[b * (a.NV + 1) + 1 + v] * a.store_vs;
     else return a.src + (long)v * a.src_vs + (long)b * a.src_bs;
 }
+
+// Sources of batch item b: uniform over the workgroup (b = blockIdx.y), one scalar load ahead of the view loop.
+__device__ __forceinline__ int source_count(const WarpAggArgs& a, int b) { return a.nsrc ? a.nsrc[b] : a.NV; }
 
 // Forms whose INDEXED instantiation leaves the register budget class of the plain one (compiler's counts, gfx950, -O3:
 // one-thread form at C = 16: 72-80 -> 84-106 VGPRs, 6-7 -> 4-5 waves per SIMD; lane-split form at (16, 8) and (64, 8):
@@ -113,7 +119,8 @@ __global__ void __launch_bounds__(PX * DMAX) warp_agg_fwd_kernel(WarpAggArgs a) 
     for (int g = 0; g < G; ++g) acc[g] = 0.0f;
     float wsum = 1e-8f;
 
-    for (int v = 0; v < a.NV; ++v) {
+    const int nv = source_count(a, b);
+    for (int v = 0; v < nv; ++v) {
         mv::RT m;
         {
             const float* r = a.rt + ((long)b * a.NV + v) * 12;  // wave-uniform
@@ -236,7 +243,8 @@ __global__ void __launch_bounds__(64 * DMAX) warp_agg_fwd_lanes_kernel(WarpAggAr
     for (int k = 0; k < GPL; ++k) acc[k] = 0.0f;
     float wsum = 1e-8f;
 
-    for (int v = 0; v < a.NV; ++v) {
+    const int nv = source_count(a, b);
+    for (int v = 0; v < nv; ++v) {
         mv::RT m;
         {
             const float* r = a.rt + ((long)b * a.NV + v) * 12;
@@ -368,7 +376,8 @@ __global__ void __launch_bounds__(256) warp_agg_fwd_wave_kernel(WarpAggArgs a) {
     for (int k = 0; k < GPL; ++k) acc[k] = 0.0f;
     float wsum = 1e-8f;
 
-    for (int v = 0; v < a.NV; ++v) {
+    const int nv = source_count(a, b);
+    for (int v = 0; v < nv; ++v) {
         mv::RT m;
         const float* r = a.rt + ((long)b * a.NV + v) * 12;  // wave-uniform
 #pragma unroll
@@ -2197,7 +2206,7 @@ static int warp_agg_fwd_any(const float* ref_feat, const float* src_feat, const 
                             float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w,
                             int Hs, int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride,
                             int group_cor, int attn_fuse_d, float attn_temp, int variant, const int* views, long store_vs,
-                            void* stream) {
+                            const int* nsrc, void* stream) {
     if (!ref_feat || !src_feat || !rt || !hypo || !out) return MVSTER_ERR_NULL;
     if (B <= 0 || NV <= 0 || D <= 0 || D > kMaxFwdD || h <= 0 || w <= 0 || Hs <= 0 || Ws <= 0) return MVSTER_ERR_SHAPE;
     if (!group_cor && G != C) return MVSTER_ERR_SHAPE;
@@ -2207,14 +2216,14 @@ static int warp_agg_fwd_any(const float* ref_feat, const float* src_feat, const 
     a.B = B; a.NV = NV; a.D = D; a.h = h; a.w = w; a.Hs = Hs; a.Ws = Ws;
     a.attn_temp = attn_temp; a.sqrt_c = sqrtf((float)C); a.fuse_d = attn_fuse_d;
     a.inv_min = a.inv_max = a.dvals = nullptr; a.hypo_out = nullptr; a.ndv = 0;
-    a.views = views; a.store_vs = store_vs;
+    a.views = views; a.store_vs = store_vs; a.nsrc = nsrc;
     hipStream_t s = (hipStream_t)stream;
-    if (views && (variant == 4 || variant == 5)) return MVSTER_ERR_UNSUPPORTED;   // (forms kept for the record: plain only)
+    if ((views || nsrc) && (variant == 4 || variant == 5)) return MVSTER_ERR_UNSUPPORTED;   // (forms kept for the record: plain only)
     // variant: 0 = choose; 1 = one thread per (pixel, d); 2 = workgroup-level lane split (C >= 16);
     // 3 = wave-local kernel (what 0 picks whenever it applies); 4 = pixel-major kernel (faster on cache-resident inputs,
     // slower inside the forward: kept as a tested alternative)
 #ifdef MVSTER_PROBES
-    if (!views && group_cor && (D == 4 || D == 8) && (variant == 4 || (variant == 0 && C <= 16 && g_pix))) {
+    if (!views && !nsrc && group_cor && (D == 4 || D == 8) && (variant == 4 || (variant == 0 && C <= 16 && g_pix))) {
         int rc = MVSTER_ERR_UNSUPPORTED;
         if (C == 8 && G == 4) rc = dispatch_fwd_pix<8, 4>(a, s);
         else if (C == 8 && G == 8) rc = dispatch_fwd_pix<8, 8>(a, s);
@@ -2273,7 +2282,7 @@ extern "C" int mvster_warp_agg_fwd(const float* ref_feat, const float* src_feat,
                                    int Hs, int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride,
                                    int group_cor, int attn_fuse_d, float attn_temp, int variant, void* stream) {
     return warp_agg_fwd_any(ref_feat, src_feat, rt, hypo, out, wsum_out, B, NV, C, G, D, h, w, Hs, Ws, ref_batch_stride,
-                            src_view_stride, src_batch_stride, group_cor, attn_fuse_d, attn_temp, variant, nullptr, 0, stream);
+                            src_view_stride, src_batch_stride, group_cor, attn_fuse_d, attn_temp, variant, nullptr, 0, nullptr, stream);
 }
 
 // mvster_warp_agg_fwd reading its maps from a level store [V, h, w, C] through a DEVICE table views [B, 1 + NV] (column 0
@@ -2286,7 +2295,32 @@ extern "C" int mvster_warp_agg_fwd_indexed(const float* store, const int* views,
     if (!store || !views) return MVSTER_ERR_NULL;
     if (V <= 0 || C <= 0) return MVSTER_ERR_SHAPE;
     return warp_agg_fwd_any(store, store, rt, hypo, out, wsum_out, B, NV, C, G, D, h, w, h, w, 0, 0, 0, group_cor, attn_fuse_d,
-                            attn_temp, variant, views, (long)h * w * C, stream);
+                            attn_temp, variant, views, (long)h * w * C, nullptr, stream);
+}
+
+// The two entries above with a source count per batch item: nsrc is a DEVICE array [B], item b aggregates its first nsrc[b]
+// sources (1 <= nsrc[b] <= NV, NOT checked here: the caller validates the counts before it uploads them, as it does the
+// table).  NV stays the capacity -- rt is [B, NV, 12] and the table [B, 1 + NV] -- and the rt rows, table entries and maps of
+// the slots beyond the count are never read.  Same kernels, and with count n the bits of the uncounted entry at NV = n on the
+// first n sources.  MVSTER_ERR_UNSUPPORTED for the same forms as the uncounted entries.
+extern "C" int mvster_warp_agg_fwd_counted(const float* ref_feat, const float* src_feat, const float* rt, const float* hypo,
+                                           float* out, float* wsum_out, int B, int NV, int C, int G, int D, int h, int w,
+                                           int Hs, int Ws, long ref_batch_stride, long src_view_stride, long src_batch_stride,
+                                           int group_cor, int attn_fuse_d, float attn_temp, int variant, const int* nsrc,
+                                           void* stream) {
+    if (!nsrc) return MVSTER_ERR_NULL;
+    return warp_agg_fwd_any(ref_feat, src_feat, rt, hypo, out, wsum_out, B, NV, C, G, D, h, w, Hs, Ws, ref_batch_stride,
+                            src_view_stride, src_batch_stride, group_cor, attn_fuse_d, attn_temp, variant, nullptr, 0, nsrc, stream);
+}
+
+extern "C" int mvster_warp_agg_fwd_indexed_counted(const float* store, const int* views, const float* rt, const float* hypo,
+                                                   float* out, float* wsum_out, int V, int B, int NV, int C, int G, int D, int h,
+                                                   int w, int group_cor, int attn_fuse_d, float attn_temp, int variant,
+                                                   const int* nsrc, void* stream) {
+    if (!store || !views || !nsrc) return MVSTER_ERR_NULL;
+    if (V <= 0 || C <= 0) return MVSTER_ERR_SHAPE;
+    return warp_agg_fwd_any(store, store, rt, hypo, out, wsum_out, B, NV, C, G, D, h, w, h, w, 0, 0, 0, group_cor, attn_fuse_d,
+                            attn_temp, variant, views, (long)h * w * C, nsrc, stream);
 }
 
 extern "C" int mvster_gather_views(const float* store, const int* views, float* out, int V, int B, int N, long map_floats,

@@ -356,13 +356,16 @@ class MVS4net(nn.Module):
 
     @torch.no_grad()
     def _cascade_eval(self, pyramid, regs, N, B, H, W, rts, depth_values, depth_interval, hypo0=None, teacher=None,
-                      capture=None, join=None, views=None):
+                      capture=None, join=None, views=None, nsrc=None):
         """The cascade after the FPN, shared by the per-sample forward and the scan runner (``mvster_amd.scan``).
         ``pyramid[s]`` is the level stage ``s`` reads: the view-major batch [N*B,1,h,w,C] of ONE sample (``views`` None), or
         the level STORE [V,h,w,C] of a whole scan with ``views`` the device int32 table [B,N] of the sample's view numbers
         (column 0 = the reference view) -- the warp kernel then reads the maps by index and everything else is the same
         launches on the same operands.  ``join``: called before stage 3 (the fine FPN levels' stream).  The store form has
-        no ``mono_feat`` entries (they are views of the per-sample pyramid) and no ``feats_cl`` capture."""
+        no ``mono_feat`` entries (they are views of the per-sample pyramid) and no ``feats_cl`` capture.  ``nsrc``: source
+        counts [B] (``ops.warp_agg_fwd_cl``) for the warp launch of every stage -- item b runs with its first ``nsrc[b]``
+        sources, the bits of the forward on those views alone; the hypotheses are then never scheduled inside the warp
+        launch (``fuse_hypotheses``: that entry has no counted form)."""
         outputs = {}
         prev = None
         for s in range(self.num_stage):
@@ -382,7 +385,8 @@ class MVS4net(nn.Module):
             cor = hypo = None
             if teacher is not None and name in teacher:
                 hypo = teacher[name].contiguous()
-            elif views is None and self.inverse_depth and self.group_cor and self.warp_variant == 0 and self.fuse_hypotheses:
+            elif (views is None and nsrc is None and self.inverse_depth and self.group_cor and self.warp_variant == 0
+                  and self.fuse_hypotheses):
                 # the stage's hypotheses are computed inside the warp launch (one kernel and one dependency edge less per stage)
                 fused = ops.warp_agg_fwd_sched_cl(
                     ref_cl.contiguous(), src_cl.contiguous(), rt, G, self.stage_splits[s], self.attn_fuse_d, float(self.attn_temp),
@@ -396,10 +400,10 @@ class MVS4net(nn.Module):
                 hypo = self._hypotheses(s, depth_values, depth_interval, prev, h, w)
             if cor is None and views is not None:
                 cor = ops.warp_agg_fwd_indexed_cl(f, views, rt, hypo, G, self.group_cor, self.attn_fuse_d,
-                                                  float(self.attn_temp), variant=self.warp_variant)
+                                                  float(self.attn_temp), variant=self.warp_variant, nsrc=nsrc)
             elif cor is None:
                 cor = ops.warp_agg_fwd_cl(ref_cl, src_cl, rt, hypo, G, self.group_cor, self.attn_fuse_d,
-                                          float(self.attn_temp), variant=self.warp_variant)
+                                          float(self.attn_temp), variant=self.warp_variant, nsrc=nsrc)
             plan = regs[s]
             want_logits = capture is not None
             if isinstance(plan, Reg2dPlan):

@@ -282,9 +282,10 @@ def to_channels_last(feat_nchw):
 
 
 def warp_agg_fwd_cl(ref_cl, src_cl, rt, hypo, G, group_cor=True, attn_fuse_d=True, attn_temp=2.0, want_wsum=False,
-                    variant=0):
+                    variant=0, nsrc=None):
     """ref_cl [B,h,w,C], src_cl [NV,B,Hs,Ws,C], rt [B,NV,12], hypo [B,D,h,w] ->
-    cor_feats channels-last [B,D,h,w,G] (and wsum [B,D,h,w]).  mvs4net_utils.py:1025-1060."""
+    cor_feats channels-last [B,D,h,w,G] (and wsum [B,D,h,w]).  mvs4net_utils.py:1025-1060.  ``nsrc`` [B] (``_source_counts``):
+    batch item b aggregates its first ``nsrc[b]`` sources only, the bits of this call on ``src_cl[:n]``, ``rt[:, :n]``."""
     for t, n in ((ref_cl, "ref"), (src_cl, "src"), (rt, "rt"), (hypo, "hypo")):
         _chk(t, "warp_agg_fwd:" + n)
     B, h, w, C = ref_cl.shape
@@ -294,9 +295,16 @@ def warp_agg_fwd_cl(ref_cl, src_cl, rt, hypo, G, group_cor=True, attn_fuse_d=Tru
         raise RuntimeError("warp_agg_fwd: inconsistent shapes")
     out = torch.empty(B, D, h, w, G, device=ref_cl.device, dtype=torch.float32)
     wsum = torch.empty(B, D, h, w, device=ref_cl.device, dtype=torch.float32) if want_wsum else None
-    rc = _lib.load().mvster_warp_agg_fwd(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), B, NV,
-                                         C, G, D, h, w, Hs, Ws, h * w * C, B * Hs * Ws * C, Hs * Ws * C,
-                                         int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant), _stream())
+    if nsrc is None:
+        rc = _lib.load().mvster_warp_agg_fwd(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), B, NV,
+                                             C, G, D, h, w, Hs, Ws, h * w * C, B * Hs * Ws * C, Hs * Ws * C,
+                                             int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant), _stream())
+    else:
+        nsrc = _source_counts(nsrc, NV, B, ref_cl.device, "warp_agg_fwd")
+        rc = _lib.load().mvster_warp_agg_fwd_counted(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum),
+                                                     B, NV, C, G, D, h, w, Hs, Ws, h * w * C, B * Hs * Ws * C, Hs * Ws * C,
+                                                     int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant),
+                                                     _ptr(nsrc), _stream())
     _lib.check(rc, "warp_agg_fwd")
     return (out, wsum) if want_wsum else out
 
@@ -315,13 +323,39 @@ def check_view_table(views, V, what="warp_agg_fwd_indexed"):
     return t.astype(np.int32)
 
 
+def check_source_counts(counts, NV, B, what="warp_agg_fwd"):
+    """HOST source counts (anything ``numpy.asarray`` takes) -> contiguous int32 [B], after checking ``1 <= n <= NV``: the
+    counted kernels read them from device memory and trust them, as they do the view table."""
+    import numpy as np
+    c = np.asarray(counts, dtype=np.int64)                # (ascontiguousarray would turn a scalar into [1])
+    if c.ndim != 1 or c.shape[0] != B:
+        raise RuntimeError("%s: the source counts must be [B] = [%d], got %s" % (what, B, c.shape))
+    bad = np.argwhere((c < 1) | (c > NV))
+    if len(bad):
+        r = int(bad[0][0])
+        raise RuntimeError("%s: source count %d (row %d) lies outside 1..NV = %d" % (what, c[r], r, NV))
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+def _source_counts(nsrc, NV, B, device, what):
+    """``nsrc`` of the counted warp calls -> device int32 [B]: a host array is checked (``check_source_counts``) and uploaded,
+    an int32 tensor already on the GPU is used as it is -- the caller vouches for its values."""
+    if torch.is_tensor(nsrc) and nsrc.is_cuda:
+        if nsrc.dtype != torch.int32 or not nsrc.is_contiguous() or nsrc.device != device or tuple(nsrc.shape) != (B,):
+            raise RuntimeError("%s: device source counts must be contiguous int32 [B] = [%d] on the maps' device" % (what, B))
+        return nsrc
+    return torch.from_numpy(check_source_counts(nsrc.numpy() if torch.is_tensor(nsrc) else nsrc, NV, B, what)).to(device)
+
+
 def warp_agg_fwd_indexed_cl(store, views, rt, hypo, G, group_cor=True, attn_fuse_d=True, attn_temp=2.0, want_wsum=False,
-                            variant=0):
+                            variant=0, nsrc=None):
     """``warp_agg_fwd_cl`` reading its maps from a level store: store [V,h,w,C] (one pyramid level of every view of a
     scan), views [B,1+NV] (column 0 = the reference view, the rest its sources; repeats allowed), rt [B,NV,12], hypo
     [B,D,h,w] -> cor_feats [B,D,h,w,G] (and wsum), the bits of ``warp_agg_fwd_cl(store[views[:,0]], store[views[:,1:]].T...)``.
     ``views`` on the host (array / list / CPU tensor) is range-checked and uploaded here; an int32 tensor already on the GPU is
-    used as it is -- the caller vouches for it (``check_view_table``), the kernel does not look."""
+    used as it is -- the caller vouches for it (``check_view_table``), the kernel does not look.  ``nsrc`` [B]
+    (``_source_counts``): item b aggregates its first ``nsrc[b]`` sources; the table entries, ``rt`` rows and maps of its other
+    slots are not read (the host check still wants every table entry to be a valid index)."""
     for t, n in ((store, "store"), (rt, "rt"), (hypo, "hypo")):
         _chk(t, "warp_agg_fwd_indexed:" + n)
     if store.dim() != 4:
@@ -340,9 +374,16 @@ def warp_agg_fwd_indexed_cl(store, views, rt, hypo, G, group_cor=True, attn_fuse
         raise RuntimeError("warp_agg_fwd_indexed: inconsistent shapes")
     out = torch.empty(B, D, h, w, G, device=store.device, dtype=torch.float32)
     wsum = torch.empty(B, D, h, w, device=store.device, dtype=torch.float32) if want_wsum else None
-    rc = _lib.load().mvster_warp_agg_fwd_indexed(_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), V, B, NV,
-                                                 C, G, D, h, w, int(group_cor), int(attn_fuse_d), float(attn_temp),
-                                                 int(variant), _stream())
+    if nsrc is None:
+        rc = _lib.load().mvster_warp_agg_fwd_indexed(_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), V, B,
+                                                     NV, C, G, D, h, w, int(group_cor), int(attn_fuse_d), float(attn_temp),
+                                                     int(variant), _stream())
+    else:
+        nsrc = _source_counts(nsrc, NV, B, store.device, "warp_agg_fwd_indexed")
+        rc = _lib.load().mvster_warp_agg_fwd_indexed_counted(_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out),
+                                                             _ptr(wsum), V, B, NV, C, G, D, h, w, int(group_cor),
+                                                             int(attn_fuse_d), float(attn_temp), int(variant), _ptr(nsrc),
+                                                             _stream())
     if rc == _lib.ERR_UNSUPPORTED:
         # a kernel form that is not instantiated indexed (csrc/warp_agg.hip, kIndexedOneThread / kIndexedLanes), or no kernel
         # at all: one gather launch into the view-major batch, then the plain entry -- which raises in the second case
@@ -350,7 +391,7 @@ def warp_agg_fwd_indexed_cl(store, views, rt, hypo, G, group_cor=True, attn_fuse
         maps = torch.empty(N, B, h, w, C, device=store.device, dtype=torch.float32)
         _lib.check(_lib.load().mvster_gather_views(_ptr(store), _ptr(views), _ptr(maps), V, B, N, h * w * C, _stream()),
                    "gather_views")
-        return warp_agg_fwd_cl(maps[0], maps[1:], rt, hypo, G, group_cor, attn_fuse_d, attn_temp, want_wsum, variant)
+        return warp_agg_fwd_cl(maps[0], maps[1:], rt, hypo, G, group_cor, attn_fuse_d, attn_temp, want_wsum, variant, nsrc)
     _lib.check(rc, "warp_agg_fwd_indexed")
     return (out, wsum) if want_wsum else out
 

@@ -25,7 +25,10 @@ must have one admissible size.
 
 The reference's two other evaluation loaders (``crop_rows`` = ``datasets/tanks.py``, ``img_wh`` = ``datasets/eth3d.py``,
 ``depth_range_kind="min_max"`` for both): a crop, or a resize of every view from its own native
-size to one target, in the same launch.  ``plan_inputs`` is the host side of all three.
+size to one target, in the same launch.  ``plan_inputs`` is the host side of all three.  Those loaders run a reference view
+whose pair list is shorter than ``nviews - 1`` with the views it has; ``short_sources="fewer_views"`` does the same on the one
+captured cascade: the warp launches read a per-sample source count from the sample's row (``ops.warp_agg_fwd_indexed_cl(...,
+nsrc=...)``).
 """
 import collections
 import os
@@ -36,11 +39,21 @@ import torch
 
 from . import formats, ops
 
-ScanPlan = collections.namedtuple("ScanPlan", "ref_views view_table proj depth_values fusion_pairs")
+ScanPlan = collections.namedtuple("ScanPlan", "ref_views view_table proj depth_values fusion_pairs source_counts")
 ScanPlan.__doc__ = """Host planning of a scan (pure NumPy).  ``ref_views`` [R] view numbers that get a depth map, ``view_table``
 int32 [R,nviews] (column 0 = the reference view, then its sources cut / padded as ``formats.eval_view_list`` does),
 ``proj`` dict stage1..4 -> [V,2,4,4] (``formats.stage_proj_matrices`` over ALL views: a sample's stack is
-``proj[stage][view_table[r]]``), ``depth_values`` [R,ndv], ``fusion_pairs`` the pairs with sources, full source lists."""
+``proj[stage][view_table[r]]``), ``depth_values`` [R,ndv], ``fusion_pairs`` the pairs with sources, full source lists,
+``source_counts`` int32 [R]: the sources row r runs with -- ``nviews - 1`` everywhere unless ``short_sources="fewer_views"``,
+where a shorter list keeps its length and the unused slots of its row hold the reference view's own number (a valid
+index with a finite projection stack, which the counted kernels never read)."""
+
+SHORT_SOURCES = (None, "fewer_views")
+
+
+def _check_short_sources(short_sources):
+    if short_sources not in SHORT_SOURCES:
+        raise RuntimeError("infer_scan: short_sources = %r (None or 'fewer_views')" % (short_sources,))
 
 
 def _as_pairs(pairs, V):
@@ -57,7 +70,7 @@ def _as_pairs(pairs, V):
 DEPTH_RANGE_KINDS = ("min_interval", "min_max")
 
 
-def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192, depth_range_kind="min_interval"):
+def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192, depth_range_kind="min_interval", short_sources=None):
     """Per-view quarter-resolution intrinsics ``Ks`` [V,3,3] and extrinsics ``Es`` [V,4,4] (``formats.read_cam_file``),
     ``depth_ranges`` [V] of (depth_min, depth_interval) or ready ``depth_values`` [V,ndv], ``pairs`` as
     ``formats.read_pair_file`` -> ScanPlan.  View list per reference view as ``formats.eval_view_list`` +
@@ -65,7 +78,13 @@ def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192, depth_range_ki
     reference views without sources dropped.  ``depth_range_kind="min_max"``: ``depth_ranges`` [V,2] holds (depth_min,
     depth_max), the two values ``datasets/tanks.py:131`` and ``datasets/eth3d.py:133`` hand to the forward, and goes through
     as a sample's ``depth_values`` (ndv = 2) -- the forward reads the first and the last entry and the count, so this is a
-    different input from the 192 values the default builds, not a shorthand for them."""
+    different input from the 192 values the default builds, not a shorthand for them.
+
+    ``short_sources="fewer_views"``: a reference view with fewer than ``nviews - 1`` sources runs with the sources it has, as
+    ``datasets/tanks.py:68`` and ``datasets/eth3d.py`` do (they cut a list and never pad it) -- ``source_counts`` says how
+    many, nothing is padded by repetition.  With the DTU loader's inputs this DIFFERS from ``general_eval4``'s padding: the
+    result is the forward on the unpadded sample."""
+    _check_short_sources(short_sources)
     if depth_range_kind not in DEPTH_RANGE_KINDS:
         raise RuntimeError("infer_scan: depth_range_kind = %r (one of %s)" % (depth_range_kind, ", ".join(DEPTH_RANGE_KINDS)))
     Ks = np.asarray(Ks, dtype=np.float32)
@@ -83,12 +102,15 @@ def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192, depth_range_ki
     if dr.ndim != 2 or dr.shape[0] != V or dr.shape[1] < 2:
         raise RuntimeError("infer_scan: depth_ranges must be [V,2] (depth_min, depth_interval) or depth_values [V,ndv], "
                            "got %s for %d views" % (dr.shape, V))
-    ref_views, table, dvs, fusion_pairs = [], [], [], []
+    ref_views, table, dvs, fusion_pairs, counts = [], [], [], [], []
     for r, srcs in pairs:
         if not srcs:
             continue                                                        # (read_pair_file drops these too)
         fusion_pairs.append((r, list(srcs)))
-        if len(srcs) < nviews:
+        counts.append(min(len(srcs), nviews - 1) if short_sources == "fewer_views" else nviews - 1)
+        if short_sources == "fewer_views":
+            srcs = srcs + [r] * (nviews - len(srcs))                        # (unused slots: the reference's own number)
+        elif len(srcs) < nviews:
             srcs = srcs + [srcs[0]] * (nviews - len(srcs))                  # general_eval4.py:47-49
         ref_views.append(r)
         table.append([r] + srcs[:nviews - 1])
@@ -102,7 +124,8 @@ def plan_scan(Ks, Es, depth_ranges, pairs, nviews=5, ndepths=192, depth_range_ki
     if not ref_views:
         raise RuntimeError("infer_scan: no reference view with a source view in pairs")
     return ScanPlan(np.array(ref_views, dtype=np.int64), np.array(table, dtype=np.int32),
-                    formats.stage_proj_matrices(Ks, Es), np.stack(dvs).astype(np.float32), fusion_pairs)
+                    formats.stage_proj_matrices(Ks, Es), np.stack(dvs).astype(np.float32), fusion_pairs,
+                    np.array(counts, dtype=np.int32))
 
 
 def store_bytes(V, H, W, base_channels=8):
@@ -233,7 +256,7 @@ ScanInputs.__doc__ = """What ``plan_inputs`` makes of a scan's images and intrin
 [(Hs, Ws)] per view; the target ``H``, ``W``; ``crop`` (top, bottom, left, right); ``Ks`` adjusted to the prepared images;
 ``prepare``: the images go through ``ops.load_pack_images_u8`` (uint8 images with one of the three preparations, even
 where it leaves the size alone), and ``source_bytes`` is what that reads; ``exact_sources``: the loader cuts source lists
-and never pads them (``_check_source_counts``)."""
+and never pads them (``_check_source_counts``, unless ``short_sources="fewer_views"`` runs them as they are)."""
 
 
 def plan_inputs(images, Ks, max_h=None, max_w=None, crop_rows=None, img_wh=None, Es=None):
@@ -268,14 +291,16 @@ def plan_inputs(images, Ks, max_h=None, max_w=None, crop_rows=None, img_wh=None,
 
 
 def _check_source_counts(pairs, nviews, view_ids=None):
-    """The dataset modes cut a source list to ``nviews - 1`` and never pad it (datasets/tanks.py:68): a shorter list is
-    refused here, naming the view."""
+    """The dataset modes cut a source list to ``nviews - 1`` and never pad it (datasets/tanks.py:68).  Without
+    ``short_sources="fewer_views"`` -- which runs such a view with the sources it has, the loaders' behaviour -- a shorter
+    list is refused here, naming the view and the keyword."""
     for r, srcs in pairs:
         if 0 < len(srcs) < nviews - 1:
             name = int(r) if view_ids is None else int(view_ids[int(r)])
             raise RuntimeError("infer_scan: reference view %d has %d source views, fewer than nviews - 1 = %d: the Tanks and "
                                "Temples / ETH3D loaders would run it with %d views, but a captured graph has one view count, "
-                               "and padding the list (as the DTU loader does) would change the result; lower nviews or drop "
+                               "and padding the list (as the DTU loader does) would change the result; pass "
+                               "short_sources='fewer_views' to run it as the loaders do, lower nviews or drop "
                                "the view from pairs" % (name, len(srcs), nviews - 1, len(srcs) + 1))
 
 
@@ -307,6 +332,7 @@ class _Instance:
         self.buf = torch.zeros(runner.row, dtype=torch.float32, device=dev)
         n = runner.nviews
         self.views = self.buf[:n].view(torch.int32).view(1, n)
+        self.nsrc = self.buf[n:n + 1].view(torch.int32) if runner.counted else None   # [1]: this sample's source count
         self.pms = [self.buf[o:o + n * 32].view(1, n, 2, 4, 4) for o in runner.proj_off]
         self.dv = self.buf[runner.dv_off:runner.dv_off + runner.ndv].view(1, runner.ndv)
         self.graph = None
@@ -319,7 +345,8 @@ class _Instance:
         depth_interval = None
         if not model.inverse_depth:
             depth_interval = (self.dv[:, -1] - self.dv[:, 0]) / self.dv.size(1)
-        return model._cascade_eval(self.stores, self.regs, n, 1, H, W, rts, self.dv, depth_interval, views=self.views)
+        return model._cascade_eval(self.stores, self.regs, n, 1, H, W, rts, self.dv, depth_interval, views=self.views,
+                                   nsrc=self.nsrc)
 
     def capture(self, model):
         self.graph = torch.cuda.CUDAGraph()
@@ -328,18 +355,20 @@ class _Instance:
 
 
 class _ScanRunner:
-    """Level stores + captured cascades of one (model state, V, H, W, nviews, ndv) combination; the captured instances
-    grow with the largest ``in_flight`` asked for."""
+    """Level stores + captured cascades of one (model state, V, H, W, nviews, ndv, counted) combination; the captured
+    instances grow with the largest ``in_flight`` asked for.  ``counted``: the cascade's warp launches are the counted
+    entries and read the sample's source count from its row -- one graph for every count from 1 to ``nviews - 1``."""
 
-    def __init__(self, model, V, H, W, nviews, ndv, stamp):
+    def __init__(self, model, V, H, W, nviews, ndv, stamp, counted=False):
         self.dev = next(model.parameters()).device
-        self.V, self.H, self.W, self.nviews, self.ndv, self.stamp = V, H, W, nviews, ndv, stamp
+        self.V, self.H, self.W, self.nviews, self.ndv, self.stamp, self.counted = V, H, W, nviews, ndv, stamp, counted
         c = model.feature.out_channels                                       # [8c, 4c, 2c, c] for stages 1..4
         self.stores = [torch.empty(V, H >> (3 - s), W >> (3 - s), c[s], device=self.dev, dtype=torch.float32)
                        if s < model.num_stage else None for s in range(4)]
-        # per-sample row: view table (int32 bits), one projection stack per stage, depth_values; 64-float segments
+        # per-sample row: view table and source count (int32 bits), one projection stack per stage, depth_values; 64-float
+        # segments
         seg = lambda k: (k + 63) // 64 * 64
-        off = seg(nviews)
+        off = seg(nviews + 1)
         self.proj_off = []
         for _ in range(model.num_stage):
             self.proj_off.append(off)
@@ -349,11 +378,13 @@ class _ScanRunner:
         self.plans = model._get_plans()                                      # (kept alive: the graphs hold pointers into them)
         self.instances = []
 
-    def rows(self, plan, num_stage):
-        """All per-sample rows of a scan on the host: [R, row] float32 (the view numbers as raw int32 bits)."""
+    def rows(self, plan, num_stage, entries=None):
+        """All per-sample rows of a scan on the host: [R, row] float32 (the store entries and the count as raw int32 bits).
+        ``entries``: the store entries [R,nviews] the warp kernel reads where they are not the view numbers (``_short_entries``)."""
         R = len(plan.ref_views)
         host = np.zeros((R, self.row), dtype=np.float32)
-        host[:, :self.nviews] = plan.view_table.view(np.float32)
+        host[:, :self.nviews] = np.ascontiguousarray(plan.view_table if entries is None else entries, dtype=np.int32).view(np.float32)
+        host[:, self.nviews] = plan.source_counts.view(np.float32)
         for s in range(num_stage):
             pm = plan.proj["stage%d" % (s + 1)][plan.view_table]            # [R,nviews,2,4,4]
             host[:, self.proj_off[s]:self.proj_off[s] + self.nviews * 32] = pm.reshape(R, -1)
@@ -364,49 +395,73 @@ class _ScanRunner:
 _RUNNERS = weakref.WeakKeyDictionary()          # model -> _ScanRunner (one scan shape resident per model: the stores are large)
 
 
-def _runner(model, V, H, W, nviews, ndv):
+def _runner(model, V, H, W, nviews, ndv, counted=False):
     stamp = model._state_stamp()
     from .graph import ForwardCache
     # (the switches that pick kernels or launches: flipped between two calls they are a different graph)
     cfg = ForwardCache.key(model, [torch.empty(1, 3, 1, 1)], {}, torch.empty(1, ndv))[-1]
-    key = (V, H, W, nviews, ndv, stamp, cfg)
+    key = (V, H, W, nviews, ndv, stamp, cfg, counted)
     hit = _RUNNERS.get(model)
     if hit is None or hit[0] != key:
         if hit is not None:
             hit[1].instances.clear()             # the old graphs and stores go now, before anything new is allocated or captured
             hit = None
             del _RUNNERS[model]
-        hit = _RUNNERS[model] = (key, _ScanRunner(model, V, H, W, nviews, ndv, stamp))
+        hit = _RUNNERS[model] = (key, _ScanRunner(model, V, H, W, nviews, ndv, stamp, counted))
     return hit[1]
 
 
-def _run_fpn(model, runner, kind, dev_images, chunk, packed=None):
+def _short_entries(plan, V, nviews):
+    """Store entries for the reference views that run with fewer sources -> (entries [R,nviews], pages, number of store
+    entries).  The per-sample forward runs the FPN on a sample's OWN ``1 + n`` images, and ``conv_plan`` picks kernels by
+    batch: in a batch of ``1 + n < nviews`` images a view's features need not carry the bits they have in a batch of
+    ``nviews`` (at 128 x 128 a batch of 2 takes other kernels than one of 4 in 12 of the FPN's 18 layers).  So the views of
+    the samples with n sources get further entries behind the scan's V, computed in batches of ``1 + n``; ``pages`` lists
+    them as (batch, views, first entry) per distinct short count, and the rows of those samples name these entries."""
+    entries = np.array(plan.view_table, dtype=np.int32)
+    pages, first = [], V
+    for n in sorted(set(int(c) for c in plan.source_counts if c < nviews - 1)):
+        rows = np.flatnonzero(plan.source_counts == n)
+        views = sorted({int(v) for r in rows for v in plan.view_table[r, :1 + n]})
+        at = {v: first + i for i, v in enumerate(views)}
+        for r in rows:
+            entries[r] = at[int(plan.view_table[r, 0])]                      # (unused slots: the reference's own entry)
+            entries[r, :1 + n] = [at[int(v)] for v in plan.view_table[r, :1 + n]]
+        pages.append((1 + n, views, first))
+        first += len(views)
+    return entries, pages, first
+
+
+def _run_fpn(model, runner, kind, dev_images, chunk, packed=None, V=None, pages=()):
     """The FPN plan over the distinct images, ``chunk`` at a time (last chunk padded by repeating its last image), each
-    level into its store.  ``packed``: the RGB0 stack where the caller has made it already.  -> number of plan runs."""
+    level into its store; then the ``pages`` of ``_short_entries``, each in batches of its own size.  ``packed``: the RGB0
+    stack where the caller has made it already; ``V``: the number of images (default: of store entries).  -> number of plan
+    runs."""
     fpn = runner.plans[0]
-    V = runner.V
+    V = runner.V if V is None else V
     if packed is None and kind == "u8":
         packed = ops.pack_images_u8(dev_images)                              # [V,1,H,W,4], one launch for the scan
     runs = 0
-    for a in range(0, V, chunk):
-        b = min(V, a + chunk)
-        idx = list(range(a, b)) + [b - 1] * (chunk - (b - a))
-        if kind == "u8":
-            x = packed[a:b] if b - a == chunk else packed[idx]
-        else:
-            x = ops.pack_images([dev_images[i:i + 1] for i in idx])
-        c0, c1, c3, f1 = fpn.trunk(x)
-        levels = list(fpn.coarse(c3, f1)) + (list(fpn.tail(c0, c1, f1)) if model.num_stage > 2 else [None, None])
-        for s in range(model.num_stage):
-            runner.stores[s][a:b].copy_(levels[s][:b - a, 0])
-        runs += 1
+    for batch, views, first in [(chunk, list(range(V)), 0)] + list(pages):
+        for a in range(0, len(views), batch):
+            b = min(len(views), a + batch)
+            idx = views[a:b] + [views[b - 1]] * (batch - (b - a))
+            if kind == "u8":
+                x = packed[idx[0]:idx[0] + batch] if idx == list(range(idx[0], idx[0] + batch)) else packed[idx]
+            else:
+                x = ops.pack_images([dev_images[i:i + 1] for i in idx])
+            c0, c1, c3, f1 = fpn.trunk(x)
+            levels = list(fpn.coarse(c3, f1)) + (list(fpn.tail(c0, c1, f1)) if model.num_stage > 2 else [None, None])
+            for s in range(model.num_stage):
+                runner.stores[s][first + a:first + b].copy_(levels[s][:b - a, 0])
+            runs += 1
     return runs
 
 
 @torch.no_grad()
 def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2,
                keep=("depth", "photometric_confidence"), ndepths=192, fpn_chunk=None, max_store_bytes=None, view_ids=None,
-               max_h=None, max_w=None, crop_rows=None, img_wh=None, depth_range_kind="min_interval"):
+               max_h=None, max_w=None, crop_rows=None, img_wh=None, depth_range_kind="min_interval", short_sources=None):
     """Depth and confidence maps of all reference views of a scan.
 
     ``images``: uint8 [V,H,W,3] (NumPy, or a tensor on the GPU) or float32 [V,3,H,W] in 0..1, or a sequence of per-view
@@ -444,27 +499,42 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
 
     Both run in the same launch; the result carries ``images`` (the prepared uint8 images on the GPU) and the adjusted
     ``Ks``, and the source bytes count towards ``max_store_bytes``, as above.  These loaders cut a source list to
-    ``nviews - 1`` and never pad it: a reference view with fewer sources raises, naming the view (a captured graph has one
-    view count, and padding would change the result).  -> ScanResult."""
+    ``nviews - 1`` and never pad it; see ``short_sources``.
+
+    ``short_sources``: what becomes of a reference view with fewer than ``nviews - 1`` sources (one without any is dropped
+    either way).  ``None``: without ``crop_rows`` / ``img_wh`` its list is padded by repeating the first source, as the DTU
+    loader does; with them it raises, naming the view.  ``"fewer_views"``: it runs with the sources it has, which is what the
+    Tanks and Temples and ETH3D loaders do -- bit-equal to the per-sample forward on the shorter sample
+    (``formats.load_tanks_sample`` / ``load_eth3d_sample``).  The scan still replays ONE captured cascade: the warp launches
+    are the counted entries (``ops.warp_agg_fwd_indexed_cl(..., nsrc=...)``) and read each sample's count from its row, on
+    every view of the scan, also where no list is short.  Allowed without ``crop_rows`` / ``img_wh`` too, where it differs
+    from ``general_eval4``'s padding: the result is then the forward on the unpadded sample.  The views of a sample with n
+    sources also get level-store entries of their own, computed in FPN batches of ``1 + n`` images as the per-sample forward
+    does (``_short_entries``: the FPN's kernels are picked by batch) -- further FPN runs and store bytes, counted in ``stats``
+    and against ``max_store_bytes``, only on scans that have such views.
+    ``stats["short_views"]`` counts the reference views that ran with fewer sources.  -> ScanResult."""
+    _check_short_sources(short_sources)
+    counted = short_sources == "fewer_views"
     inp = plan_inputs(images, Ks, max_h, max_w, crop_rows, img_wh, Es)
     kind, V, H, W, Ks = inp.kind, inp.V, inp.H, inp.W, inp.Ks
-    if inp.exact_sources:
+    if inp.exact_sources and not counted:
         _check_source_counts(_as_pairs(pairs, V), nviews, view_ids)
-    plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths, depth_range_kind)
+    plan = plan_scan(Ks, Es, depth_ranges, pairs, nviews, ndepths, depth_range_kind, short_sources)
     if in_flight < 1:
         raise RuntimeError("infer_scan: in_flight = %d" % in_flight)
     chunk = int(fpn_chunk or nviews)
     if not 1 <= chunk <= 16:
         raise RuntimeError("infer_scan: fpn_chunk = %d (1..16 images per FPN run)" % chunk)
-    need = store_bytes(V, H, W, model.feature.out_channels[-1])
+    entries, pages, store_views = _short_entries(plan, V, nviews) if counted else (None, (), V)
+    need = store_bytes(store_views, H, W, model.feature.out_channels[-1])
     if max_store_bytes is not None and inp.prepare and need + inp.source_bytes > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d and the %dx%d source images need %d + %d bytes "
                            "(%.2f GB), more than max_store_bytes = %d"
-                           % (V, H, W, max(h for h, _ in inp.sizes), max(w for _, w in inp.sizes), need, inp.source_bytes,
+                           % (store_views, H, W, max(h for h, _ in inp.sizes), max(w for _, w in inp.sizes), need, inp.source_bytes,
                               (need + inp.source_bytes) / 1e9, max_store_bytes))
     if max_store_bytes is not None and need > max_store_bytes:
         raise RuntimeError("infer_scan: the level stores of %d views of %dx%d need %d bytes (%.2f GB), more than "
-                           "max_store_bytes = %d" % (V, H, W, need, need / 1e9, max_store_bytes))
+                           "max_store_bytes = %d" % (store_views, H, W, need, need / 1e9, max_store_bytes))
     if model.training:
         raise RuntimeError("infer_scan runs the eval forward: call model.eval() first")
     dev = next(model.parameters()).device
@@ -474,12 +544,15 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     keep = tuple(keep)
     R = len(plan.ref_views)
     ops.check_view_table(plan.view_table, V, "infer_scan")                  # (the kernels trust the device table)
+    if entries is not None:
+        ops.check_view_table(entries, store_views, "infer_scan")
+    ops.check_source_counts(plan.source_counts, nviews - 1, R, "infer_scan")    # (... and the counts)
     main = torch.cuda.current_stream(dev)
     ev = {k: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for k in ("upload", "fpn", "cascade")}
 
     with torch.cuda.device(dev):
         ev["upload"][0].record(main)
-        runner = _runner(model, V, H, W, nviews, plan.depth_values.shape[1])
+        runner = _runner(model, store_views, H, W, nviews, plan.depth_values.shape[1], counted)
         packed = small = dev_images = None
         if inp.prepare:                                                      # the upload and the launch that prepares and packs
             packed, small = ops.load_pack_images_u8(inp.images, H, W, crop=inp.crop, want_u8=True, device=dev)
@@ -487,11 +560,11 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
             dev_images = inp.images.to(dev).contiguous()
         else:
             dev_images = torch.from_numpy(np.ascontiguousarray(inp.images)).to(dev)
-        samples = torch.from_numpy(runner.rows(plan, model.num_stage)).to(dev)   # all per-sample inputs: ONE upload
+        samples = torch.from_numpy(runner.rows(plan, model.num_stage, entries)).to(dev)   # all per-sample inputs: ONE upload
         ev["upload"][1].record(main)
 
         ev["fpn"][0].record(main)
-        fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk, packed)
+        fpn_runs = _run_fpn(model, runner, kind, dev_images, chunk, packed, V, pages)
         del dev_images, packed                                               # (the full-size stack goes back to the allocator)
         ev["fpn"][1].record(main)
 
@@ -537,7 +610,8 @@ def infer_scan(model, images, Ks, Es, depth_ranges, pairs, nviews=5, in_flight=2
     res = ScanResult(ref_views=plan.ref_views, pairs=plan.fusion_pairs,
                      Ks=k4[:, 1, :3, :3].copy(), Es=k4[:, 0].copy(),
                      view_ids=list(range(V)) if view_ids is None else [int(v) for v in view_ids],
-                     stats={"fpn_runs": fpn_runs, "replays": R, "captured": captured_now, "store_bytes": need}, events=ev)
+                     stats={"fpn_runs": fpn_runs, "replays": R, "captured": captured_now, "store_bytes": need,
+                            "short_views": int((plan.source_counts < nviews - 1).sum())}, events=ev)
     if inp.prepare:
         res["images"] = small
         res["stats"]["source_bytes"] = inp.source_bytes
@@ -617,20 +691,23 @@ def _dataset_keywords(dataset, kw):
 
 
 def plan_scan_folder(datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, max_h=None, max_w=None, dataset="general",
-                     crop_rows=None, img_wh=None, depth_range_kind=None):
+                     crop_rows=None, img_wh=None, depth_range_kind=None, short_sources=None):
     """Host planning of ``infer_scan_folder`` -> (the ``read_scan_folder`` dict, ScanPlan); no device work.  With ``max_h`` /
-    ``max_w``, ``crop_rows`` or ``img_wh`` the plan is made from the adjusted intrinsics (the dict keeps the files' own)."""
+    ``max_w``, ``crop_rows`` or ``img_wh`` the plan is made from the adjusted intrinsics (the dict keeps the files' own).
+    ``short_sources``: as ``infer_scan``."""
+    _check_short_sources(short_sources)
     sc = read_scan_folder(datapath, scan, interval_scale, ndepths, dataset)
     kw = _dataset_keywords(dataset, dict(crop_rows=crop_rows, img_wh=img_wh, **({} if depth_range_kind is None else
                                                                                 {"depth_range_kind": depth_range_kind})))
     crop_rows, img_wh, kind_dr = kw["crop_rows"], kw["img_wh"], kw.get("depth_range_kind", "min_interval")
     inp = plan_inputs(sc["images"], sc["Ks"], max_h, max_w, crop_rows, img_wh)
-    if inp.exact_sources:
+    if inp.exact_sources and short_sources != "fewer_views":
         _check_source_counts(_as_pairs(sc["pairs"], inp.V), nviews, sc["view_ids"])
-    return sc, plan_scan(inp.Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths, kind_dr)
+    return sc, plan_scan(inp.Ks, sc["Es"], sc["depth_ranges"], sc["pairs"], nviews, ndepths, kind_dr, short_sources)
 
 
-def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, dataset="general", **kw):
+def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndepths=192, dataset="general", short_sources=None,
+                      **kw):
     """``infer_scan`` on a scan folder in the reference's layout (``general_eval4.MVSDataset``).  The result's
     ``ref_views`` / ``pairs`` index ``view_ids`` (the file numbers).  ``max_h`` / ``max_w`` (the loader's arguments) go
     through to ``infer_scan``: a scan is taken at its native image size, as the dataset ships it.
@@ -638,11 +715,12 @@ def infer_scan_folder(model, datapath, scan, nviews=5, interval_scale=1.06, ndep
     ``dataset="tanks"``: a Tanks and Temples scan folder (``datapath`` includes the split) as ``datasets/tanks.py`` takes it --
     ``crop_rows=(28, 28)`` and ``depth_range_kind="min_max"`` unless given; the loader's default of 7 views is the caller's
     ``nviews=7``.  ``dataset="eth3d"``: ``datasets/eth3d.py`` -- ``cams_1/``, ``img_wh=(1920, 1280)`` unless given,
-    ``depth_range_kind="min_max"``."""
+    ``depth_range_kind="min_max"``.  ``short_sources="fewer_views"`` (through to ``infer_scan``) runs a reference view whose
+    pair list is shorter than ``nviews - 1`` with the sources it has, as both loaders do."""
     sc = read_scan_folder(datapath, scan, interval_scale, ndepths, dataset)
     kw = _dataset_keywords(dataset, kw)
     res = infer_scan(model, sc["images"], sc["Ks"], sc["Es"], sc["depth_ranges"], sc["pairs"], nviews=nviews,
-                     ndepths=ndepths, view_ids=sc["view_ids"], **kw)
+                     ndepths=ndepths, view_ids=sc["view_ids"], short_sources=short_sources, **kw)
     res.setdefault("images", sc["images"])                                  # (the resized ones where infer_scan scaled)
     return res
 
@@ -691,7 +769,8 @@ def write_scan_outputs(result, images, out_folder):
         Image.fromarray(imgs[int(r)]).save(os.path.join(out_folder, "images", name + ".jpg"))
 
 
-def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres_view=5, plyfilename=None, **kw):
+def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres_view=5, plyfilename=None, short_sources=None,
+                     **kw):
     """``infer_scan`` followed by ``fusion.fuse_scene`` on the device tensors: the reference's ``save_scene_depth`` +
     ``filter_depth`` (test_mvs4.py:170-268, :331-421) without leaving the GPU.  -> the ``fusion.SceneResult`` (with the
     ``ScanResult`` as its ``scan`` attribute); writes the point cloud to ``plyfilename`` if given.
@@ -701,10 +780,11 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     (with ``max_h`` / ``max_w``, ``crop_rows`` or ``img_wh``: from the prepared ones, the pixels the reference writes to
     ``images/``), not from the
     re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same, colours differ
-    by the JPEG re-encoding the reference adds."""
+    by the JPEG re-encoding the reference adds.  ``short_sources``: as ``infer_scan`` (fusion takes the pair lists as they
+    are, whatever their lengths)."""
     from . import fusion
     inp = plan_inputs(images, Ks, kw.get("max_h"), kw.get("max_w"), kw.get("crop_rows"), kw.get("img_wh"), Es)
-    scan = infer_scan(model, inp.images, Ks, Es, depth_ranges, pairs, **kw)
+    scan = infer_scan(model, inp.images, Ks, Es, depth_ranges, pairs, short_sources=short_sources, **kw)
     # (prepared: uint8 [V,Hd,Wd,3], already on the device; otherwise the input stack, which has the target size)
     kind, images = ("u8", scan["images"]) if inp.prepare else (inp.kind, inp.images)
     slot = {int(r): i for i, r in enumerate(scan["ref_views"])}
