@@ -474,6 +474,23 @@ int mvster_geo_scene_filter(const float* depth, const float* confidence, const i
                             long* wg_offsets, int R, int Smax, int V, int H, int W, float conf_thres, int thres_view,
                             float pix_thres, float rel_thres, void* stream);
 
+/* The same filter pass + scan under dynamic consistency checking instead of the fixed pixel /
+ * relative-depth thresholds.  A source passes level n when its reprojection error is below n * pix_base (fp32 product,
+ * compared in fp64) and its relative depth error below n * rel_base (fp32).  For a reference view with L real sources,
+ * geo_level [R,H,W] uint8 = the smallest n in thres_view..L with at least n sources passing level n, 0 if there is none
+ * (always 0 when L < thres_view); geo = geo_level != 0, final = photo & geo.  mask_sum = sources passing the loosest
+ * level max(L, thres_view), depth_avg = (float32 sum of their reprojected depths in pair-file order + depth_ref) /
+ * (mask_sum + 1).  Everything else -- layouts, wg_counts / wg_offsets, invalid view indices -- as for
+ * mvster_geo_scene_filter, and mvster_geo_scene_emit takes the outputs as they are.  MVSTER_ERR_UNSUPPORTED for
+ * Smax > 32 (the per-pixel level counts hold 32 sources), MVSTER_ERR_SHAPE for thres_view < 1 or a base that is not
+ * finite and positive; all arguments are checked before any launch. */
+int mvster_geo_scene_filter_dynamic(const float* depth, const float* confidence, const int* pairs, const int* ref_view,
+                                    const double* ref_mats, const double* view_mats, int* mask_sum, double* depth_avg,
+                                    unsigned char* photo_mask, unsigned char* geo_mask, unsigned char* final_mask,
+                                    unsigned char* geo_level, int* wg_counts, long* wg_offsets, int R, int Smax, int V,
+                                    int H, int W, float conf_thres, int thres_view, float pix_base, float rel_base,
+                                    void* stream);
+
 /* Emit pass: the pixels of final_mask, reference views in order and row-major inside a view, lifted to world space
  * with depth_avg in fp64 and rounded once -> points [M,3] float32 (test_mvs4.py:397-407, :413-415); colors [M,3] uint8 =
  * (image * 255) truncated (:395-396, :407).  images [V,H,W,3]: image_kind 0 = uint8 (copied: the float32 round trip

@@ -87,6 +87,7 @@ SIGNATURES = {
     "mvster_geo_filter": [_f] * 10 + [_i, _i, _i, _fl, _fl, _f],
     "mvster_geo_scene_blocks": [_i, _i, _i],
     "mvster_geo_scene_filter": [_f] * 13 + [_i] * 5 + [_fl, _i, _fl, _fl, _f],
+    "mvster_geo_scene_filter_dynamic": [_f] * 14 + [_i] * 5 + [_fl, _i, _fl, _fl, _f],
     "mvster_geo_scene_emit": [_f] * 5 + [_i, _f, _f, _f, _l, _i, _i, _i, _i, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

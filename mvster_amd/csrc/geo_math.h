@@ -1,6 +1,6 @@
 // Per-pixel arithmetic of the depth-map fusion step, shared by geo_filter.hip (one
-// reference view per launch), geo_scene.hip (a whole scan per launch) and a host build used only by the tests
-// (tests/hostmath/geo_hostmath.cpp).  Every kernel that inlines one of these functions executes the same expression
+// reference view per launch), geo_scene.hip (a whole scan per launch, fixed or dynamic thresholds) and the host builds
+// used only by the tests (tests/hostmath/geo_hostmath.cpp, geo_dyn_hostmath.cpp).  Every kernel that inlines one of these functions executes the same expression
 // tree: products that feed a sum are explicit fma, fp32 steps go through mv::*_rn, everything else is a single
 // correctly rounded operation, so neither hipcc's contraction nor the host build (-ffp-contract=off) changes a bit.
 //
@@ -63,11 +63,20 @@ struct Vote {
     float y_src;
 };
 
-// One (reference pixel, source view) vote: project the lifted pixel into the source view, sample the source depth map,
-// lift with the sampled depth, project back, apply the two tests (test_mvs4.py:283-328).  `m` = this view's 42 doubles.
-MV_HD Vote view_vote(const float* __restrict__ depth_src, int H, int W, const double* ref_mats, const double* m, int x, int y,
-                     float dref, double rx, double ry, double rz, float pix_thres, float rel_thres) {
-    Vote r;
+struct ViewError {
+    double dist;    // reprojection error in pixels (test_mvs4.py:319), fp64
+    float rel;      // relative depth error (:322-323), fp32
+    float drep;     // reprojected depth (:326), not yet thresholded
+    float x_src;    // where the pixel lands in the source view (:286-289)
+    float y_src;
+};
+
+// One (reference pixel, source view) round trip: project the lifted pixel into the source view, sample the source depth
+// map, lift with the sampled depth, project back, measure the two errors (test_mvs4.py:283-323).  `m` = this view's 42
+// doubles.  No threshold is applied: view_vote (fixed thresholds) and level_passes (dynamic consistency) do that.
+MV_HD ViewError view_error(const float* __restrict__ depth_src, int H, int W, const double* ref_mats, const double* m, int x,
+                           int y, float dref, double rx, double ry, double rz) {
+    ViewError r;
     double qx, qy, qz, kx, ky, kz;
     mat34(m, rx, ry, rz, qx, qy, qz);                              // source camera space
     mat3(m + 12, qx, qy, qz, kx, ky, kz);                          // K_src @ .
@@ -79,14 +88,24 @@ MV_HD Vote view_vote(const float* __restrict__ depth_src, int H, int W, const do
     double sx3, sy3, sz3, bx, by, bz, ux, uy, uz;
     mat3(m + 21, xs * sd, ys * sd, sd, sx3, sy3, sz3);             // inv(K_src) @ ((xs, ys, 1) * sampled)
     mat34(m + 30, sx3, sy3, sz3, bx, by, bz);                      // back in the reference camera space
-    const float drep = (float)bz;
+    r.drep = (float)bz;
     mat3(ref_mats + 9, bx, by, bz, ux, uy, uz);                    // K_ref @ .
     const float xr = (float)(ux / uz), yr = (float)(uy / uz);
     const double ex = (double)xr - (double)x, ey = (double)yr - (double)y;
-    const double dist = sqrt(fma(ex, ex, ey * ey));
-    const float rel = mv::div_rn(fabsf(mv::sub_rn(drep, dref)), dref);
-    r.ok = dist < (double)pix_thres && rel < rel_thres;
-    r.depth = r.ok ? drep : 0.0f;
+    r.dist = sqrt(fma(ex, ex, ey * ey));
+    r.rel = mv::div_rn(fabsf(mv::sub_rn(r.drep, dref)), dref);
+    return r;
+}
+
+// The fixed-threshold vote of check_geometric_consistency (test_mvs4.py:319-328) on the round trip above.
+MV_HD Vote view_vote(const float* __restrict__ depth_src, int H, int W, const double* ref_mats, const double* m, int x, int y,
+                     float dref, double rx, double ry, double rz, float pix_thres, float rel_thres) {
+    const ViewError e = view_error(depth_src, H, W, ref_mats, m, x, y, dref, rx, ry, rz);
+    Vote r;
+    r.x_src = e.x_src;
+    r.y_src = e.y_src;
+    r.ok = e.dist < (double)pix_thres && e.rel < rel_thres;
+    r.depth = r.ok ? e.drep : 0.0f;
     return r;
 }
 
@@ -99,6 +118,74 @@ MV_HD void accumulate(const Vote& v, int& count, float& dsum) {
 // (sum(reprojected depths) + depth_ref) / (votes + 1) (test_mvs4.py:385): float32 sum, float64 quotient
 MV_HD double average(float dsum, float dref, int count) {
     return (double)mv::add_rn(dsum, dref) / (double)(count + 1);
+}
+
+// ---- dynamic consistency checking: level n asks for n sources within n times the base errors ----
+
+constexpr int kMaxLevelSources = 32;   // sources per reference view the level counts below hold
+
+// source passes level n: both errors below n times their base, thresholds rounded once in fp32; NaN fails
+MV_HD bool level_passes(const ViewError& e, int n, float pix_base, float rel_base) {
+    return e.dist < (double)mv::mul_rn((float)n, pix_base) && e.rel < mv::mul_rn((float)n, rel_base);
+}
+
+// Histogram of the sources' smallest passing level: 32 bins of 8 bits (a bin holds at most 32) in four 64-bit registers,
+// bin b = level n0 + b.  Selected with compares, never indexed, so it stays in registers on the GPU.
+struct LevelCounts {
+    unsigned long long w0, w1, w2, w3;
+};
+
+MV_HD void level_bump(LevelCounts& c, int bin) {
+    const unsigned long long one = 1ull << ((bin & 7) * 8);
+    const int w = bin >> 3;
+    c.w0 += w == 0 ? one : 0ull;
+    c.w1 += w == 1 ? one : 0ull;
+    c.w2 += w == 2 ? one : 0ull;
+    c.w3 += w == 3 ? one : 0ull;
+}
+
+MV_HD int level_bin(const LevelCounts& c, int bin) {
+    const int w = bin >> 3;
+    const unsigned long long v = w == 0 ? c.w0 : (w == 1 ? c.w1 : (w == 2 ? c.w2 : c.w3));
+    return (int)((v >> ((bin & 7) * 8)) & 0xffull);
+}
+
+struct DynamicVotes {
+    int count;      // sources passing the loosest level La = max(L, n0): geo_mask_sum
+    int level;      // smallest n in n0..L with at least n sources passing level n, 0 if none: geo_level
+    float dsum;     // fp32 sum of their reprojected depths, pair-file order (failing sources add 0)
+};
+
+// One reference pixel against its row of the pair table (`pairs_row` [Smax], `vm_row` [Smax, 42]; the row ends at the
+// first index outside [0, V)).  Each source walks n upward from n0 to its smallest passing level -- the thresholds grow
+// with n, so it passes every level above -- and bumps that bin; the prefix of the bins is count_n.
+MV_HD DynamicVotes dynamic_votes(const float* __restrict__ depth, long hw, int H, int W, const int* __restrict__ pairs_row,
+                                 int Smax, int V, const double* ref_mats, const double* vm_row, int x, int y, float dref,
+                                 double rx, double ry, double rz, int n0, float pix_base, float rel_base) {
+    int L = 0;
+    while (L < Smax && (unsigned)pairs_row[L] < (unsigned)V) ++L;
+    const int bins = L > n0 ? L - n0 + 1 : 1;                      // levels n0 .. La, La = max(L, n0) the averaging level
+    LevelCounts c = {0ull, 0ull, 0ull, 0ull};
+    DynamicVotes r = {0, 0, 0.0f};
+    for (int s = 0; s < L; ++s) {
+        const ViewError e = view_error(depth + (long)pairs_row[s] * hw, H, W, ref_mats, vm_row + (long)s * kViewDoubles, x, y,
+                                       dref, rx, ry, rz);
+        int b = 0;
+        while (b < bins && !level_passes(e, n0 + b, pix_base, rel_base)) ++b;
+        Vote v;
+        v.ok = b < bins;
+        v.depth = v.ok ? e.drep : 0.0f;
+        v.x_src = e.x_src;
+        v.y_src = e.y_src;
+        if (v.ok) level_bump(c, b);
+        accumulate(v, r.count, r.dsum);
+    }
+    int cum = 0;
+    for (int b = 0; b <= L - n0; ++b) {                            // empty when L < n0: no level, nothing survives
+        cum += level_bin(c, b);
+        if (r.level == 0 && cum >= n0 + b) r.level = n0 + b;
+    }
+    return r;
 }
 
 // inv(E_ref)[:3] @ (inv(K_ref) @ ((x, y, 1) * depth), 1): a surviving pixel in world space (test_mvs4.py:399-405)

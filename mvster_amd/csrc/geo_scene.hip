@@ -91,6 +91,62 @@ __global__ void __launch_bounds__(kWG) geo_scene_filter_kernel(SceneFilterArgs a
     }
 }
 
+struct SceneDynamicArgs {
+    SceneFilterArgs f;           // pix_thres / rel_thres unused
+    unsigned char* geo_level;    // [R, H, W] the level that kept the pixel, 0 = none
+    float pix_base, rel_base;
+};
+
+// The filter pass under dynamic consistency checking (geo::dynamic_votes): same grid, same outputs and the same workgroup
+// count as geo_scene_filter_kernel, plus geo_level; the level counts are a packed histogram in registers.
+__global__ void __launch_bounds__(kWG) geo_scene_dynamic_filter_kernel(SceneDynamicArgs d) {
+    __shared__ int wave_count[kWG / 64];
+    const SceneFilterArgs& a = d.f;
+    const long hw = (long)a.H * a.W;
+    const int r = (int)(blockIdx.x / (unsigned)a.nblk), blk = (int)(blockIdx.x - (unsigned)r * (unsigned)a.nblk);
+    const long p = (long)blk * kWG + threadIdx.x;
+    const int rv = a.ref_view[r];
+    const bool inside = p < hw;
+    const bool valid = inside && (unsigned)rv < (unsigned)a.V;
+    bool fin = false;
+    if (valid) {
+        const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
+        const double* rm = a.ref_mats + (long)r * geo::kRefDoubles;
+        const float dref = a.depth[(long)rv * hw + p];
+        double rx, ry, rz;
+        geo::lift_ref(rm, x, y, dref, rx, ry, rz);
+        const geo::DynamicVotes v = geo::dynamic_votes(a.depth, hw, a.H, a.W, a.pairs + (long)r * a.Smax, a.Smax, a.V, rm,
+                                                       a.view_mats + (long)r * a.Smax * geo::kViewDoubles, x, y, dref, rx,
+                                                       ry, rz, a.thres_view, d.pix_base, d.rel_base);
+        const bool photo = a.conf[(long)rv * hw + p] > a.conf_thres;
+        const bool g = v.level != 0;
+        fin = photo && g;
+        const long o = (long)r * hw + p;
+        a.mask_sum[o] = v.count;
+        a.depth_avg[o] = geo::average(v.dsum, dref, v.count);
+        a.photo_mask[o] = photo ? 1 : 0;
+        a.geo_mask[o] = g ? 1 : 0;
+        a.final_mask[o] = fin ? 1 : 0;
+        d.geo_level[o] = (unsigned char)v.level;
+    } else if (inside) {                                                    // a view index outside the stack: nothing survives
+        const long o = (long)r * hw + p;
+        a.mask_sum[o] = 0;
+        a.depth_avg[o] = 0.0;
+        a.photo_mask[o] = 0;
+        a.geo_mask[o] = 0;
+        a.final_mask[o] = 0;
+        d.geo_level[o] = 0;
+    }
+    const unsigned long long b = __ballot(fin);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int w = 0; w < kWG / 64; ++w) c += wave_count[w];
+        a.wg_counts[blockIdx.x] = c;
+    }
+}
+
 // offsets[i] = sum(counts[0..i)), i = 0..n
 __global__ void __launch_bounds__(kScanThreads) geo_scene_scan_kernel(const int* __restrict__ counts, long* __restrict__ offsets,
                                                                       long n) {
@@ -210,6 +266,38 @@ extern "C" int mvster_geo_scene_filter(const float* depth, const float* confiden
     a.R = R; a.Smax = Smax; a.V = V; a.H = H; a.W = W; a.nblk = nwg / R; a.thres_view = thres_view;
     a.conf_thres = conf_thres; a.pix_thres = pix_thres; a.rel_thres = rel_thres;
     hipLaunchKernelGGL(geo_scene_filter_kernel, dim3((unsigned)nwg), dim3(kWG), 0, (hipStream_t)stream, a);
+    int rc = mv_check_launch();
+    if (rc != MVSTER_OK) return rc;
+    hipLaunchKernelGGL(geo_scene_scan_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, wg_counts, wg_offsets,
+                       (long)nwg);
+    return mv_check_launch();
+}
+
+extern "C" int mvster_geo_scene_filter_dynamic(const float* depth, const float* confidence, const int* pairs,
+                                               const int* ref_view, const double* ref_mats, const double* view_mats,
+                                               int* mask_sum, double* depth_avg, unsigned char* photo_mask,
+                                               unsigned char* geo_mask, unsigned char* final_mask, unsigned char* geo_level,
+                                               int* wg_counts, long* wg_offsets, int R, int Smax, int V, int H, int W,
+                                               float conf_thres, int thres_view, float pix_base, float rel_base,
+                                               void* stream) {
+    if (!depth || !confidence || !pairs || !ref_view || !ref_mats || !view_mats || !mask_sum || !depth_avg || !photo_mask ||
+        !geo_mask || !final_mask || !geo_level || !wg_counts || !wg_offsets)
+        return MVSTER_ERR_NULL;
+    if (R <= 0 || Smax <= 0 || V <= 0 || H <= 0 || W <= 0) return MVSTER_ERR_SHAPE;
+    const int nwg = mvster_geo_scene_blocks(R, H, W);
+    if (nwg < 0) return MVSTER_ERR_SHAPE;
+    if (Smax > geo::kMaxLevelSources) return MVSTER_ERR_UNSUPPORTED;       // the level counts hold 32 sources
+    if (thres_view < 1) return MVSTER_ERR_SHAPE;
+    if (!(pix_base > 0.0f) || !(rel_base > 0.0f) || std::isinf(pix_base) || std::isinf(rel_base)) return MVSTER_ERR_SHAPE;
+    SceneDynamicArgs d;
+    SceneFilterArgs& a = d.f;
+    a.depth = depth; a.conf = confidence; a.pairs = pairs; a.ref_view = ref_view; a.ref_mats = ref_mats;
+    a.view_mats = view_mats; a.mask_sum = mask_sum; a.depth_avg = depth_avg; a.photo_mask = photo_mask;
+    a.geo_mask = geo_mask; a.final_mask = final_mask; a.wg_counts = wg_counts;
+    a.R = R; a.Smax = Smax; a.V = V; a.H = H; a.W = W; a.nblk = nwg / R; a.thres_view = thres_view;
+    a.conf_thres = conf_thres; a.pix_thres = 0.0f; a.rel_thres = 0.0f;
+    d.geo_level = geo_level; d.pix_base = pix_base; d.rel_base = rel_base;
+    hipLaunchKernelGGL(geo_scene_dynamic_filter_kernel, dim3((unsigned)nwg), dim3(kWG), 0, (hipStream_t)stream, d);
     int rc = mv_check_launch();
     if (rc != MVSTER_OK) return rc;
     hipLaunchKernelGGL(geo_scene_scan_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, wg_counts, wg_offsets,

@@ -8,7 +8,9 @@ in NumPy float32, exactly as the reference computes it; everything per pixel run
 
 A whole scan -- the reference's unit of work (``filter_depth``, test_mvs4.py:331-421) -- goes through ``fuse_scene`` /
 ``filter_depth``: every map is uploaded once and three launches (``mvster_geo_scene_filter`` = filter pass + scan of the
-workgroup counts, ``mvster_geo_scene_emit``) produce the masks and the point cloud in the reference's order.
+workgroup counts, ``mvster_geo_scene_emit``) produce the masks and the point cloud in the reference's order.  With
+``method="dynamic"`` the filter pass is ``mvster_geo_scene_filter_dynamic``: dynamic consistency checking, the rule Tanks
+and Temples and ETH3D scans are fused with (not in the reference).
 """
 import collections
 import os
@@ -195,7 +197,8 @@ def scene_tables(pairs, Ks, Es):
 
 class SceneResult(dict):
     """What ``fuse_scene`` returns: a dict of tensors on the GPU (``points``, ``colors``, ``counts``, ``photo_mask``,
-    ``geo_mask``, ``final_mask``, ``geo_mask_sum``, ``depth_est_averaged``) plus ``vertices()``."""
+    ``geo_mask``, ``final_mask``, ``geo_mask_sum``, ``depth_est_averaged``; with ``method="dynamic"`` also ``geo_level``)
+    plus ``vertices()``."""
 
     def vertices(self):
         """The structured vertex array of filter_depth (test_mvs4.py:409-418) on the host, ready for ``write_ply``."""
@@ -221,8 +224,23 @@ def _scene_stack(x, dev, dtype, what):
     return x.to(dev, getattr(torch, np.dtype(dtype).name)).contiguous()
 
 
-def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=1.0, rel_thres=0.01,
-               device=None, scratch_budget=SCRATCH_BUDGET, events=None):
+FUSION_METHODS = ("normal", "dynamic")
+PIX_THRES, REL_THRES = 1.0, 0.01        # the reference's fixed thresholds (test_mvs4.py:319, :323): method "normal"
+PIX_BASE, REL_BASE = 0.25, 1 / 1300     # the base errors of the public dynamic-fusion scripts: method "dynamic"
+MAX_DYNAMIC_SOURCES = 32                # sources per reference view the dynamic filter's per-pixel level counts hold
+
+
+def _check_method(what, method, pix_thres=None, rel_thres=None):
+    if method not in FUSION_METHODS:
+        raise RuntimeError("%s: unknown fusion method %r (one of %s)" % (what, method, ", ".join(FUSION_METHODS)))
+    if method == "dynamic" and (pix_thres is not None or rel_thres is not None):
+        raise RuntimeError("%s: pix_thres / rel_thres are the fixed thresholds of method 'normal'; method 'dynamic' takes "
+                           "pix_base / rel_base" % what)
+
+
+def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=None, rel_thres=None,
+               device=None, scratch_budget=SCRATCH_BUDGET, events=None, method="normal", pix_base=PIX_BASE,
+               rel_base=REL_BASE):
     """filter_depth (test_mvs4.py:331-421) for a scan whose maps are in memory.  depths / confidences [V,H,W], images
     [V,H,W,3] (uint8, or float 0..1 as ``read_img`` returns it), Ks [V,3,3], Es [V,4,4]: NumPy arrays, tensors or
     sequences of them, indexed by the view numbers in ``pairs`` [(ref_view, [src_view, ...]), ...].  Tensors already on
@@ -232,7 +250,19 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     ``depth_est_averaged`` [R,H,W] float64.  The only host synchronisation is the read-back of the workgroup offsets
     at the view boundaries (M and ``counts``), once per call -- once per chunk of reference views when the tables and
     scan scratch of the whole scan would exceed ``scratch_budget`` bytes; the result does not depend on the chunking.
-    ``events``: a list that receives (name, start, end) torch.cuda.Event triples around the two library calls (timing)."""
+    ``events``: a list that receives (name, start, end) torch.cuda.Event triples around the two library calls (timing).
+
+    ``method``: ``"normal"`` is the reference's rule, a vote per source view within ``pix_thres`` pixels (default 1) and
+    ``rel_thres`` relative depth (default 0.01), ``thres_view`` votes to survive.  ``"dynamic"`` is dynamic consistency
+    checking: a pixel survives if for some n in ``thres_view`` .. its number of sources at least n
+    sources agree within n * ``pix_base`` pixels and n * ``rel_base`` relative depth; the result then also holds
+    ``geo_level`` [R,H,W] uint8, that n (0 = none), ``geo_mask_sum`` counts the sources agreeing at the loosest level and
+    ``depth_est_averaged`` averages over them.  At most 32 sources per reference view; ``pix_thres`` / ``rel_thres``
+    belong to ``"normal"`` and may not be given."""
+    _check_method("fuse_scene", method, pix_thres, rel_thres)
+    dynamic = method == "dynamic"
+    pix_thres = PIX_THRES if pix_thres is None else pix_thres
+    rel_thres = REL_THRES if rel_thres is None else rel_thres
     if device is None:
         devs = [m.device for x in (depths, confidences, images) for m in ([x] if isinstance(x, torch.Tensor) else
                                                                           x if not isinstance(x, np.ndarray) else [])
@@ -259,6 +289,9 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     if V != len(Ks):
         raise RuntimeError("fuse_scene: %d depth maps for %d cameras" % (V, len(Ks)))
     R, smax = tables.pair_table.shape
+    if dynamic and smax > MAX_DYNAMIC_SOURCES:
+        raise RuntimeError("fuse_scene: method 'dynamic' takes at most %d source views per reference view, a row of "
+                           "pairs has %d" % (MAX_DYNAMIC_SOURCES, smax))
     lib = _lib.load()
     nblk = lib.mvster_geo_scene_blocks(1, H, W)
     _lib.check(min(nblk, 0), "geo_scene_blocks")
@@ -267,6 +300,7 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     mask_sum = torch.empty(R, H, W, device=dev, dtype=torch.int32)
     avg = torch.empty(R, H, W, device=dev, dtype=torch.float64)
     photo, geo, final = (torch.empty(R, H, W, device=dev, dtype=torch.bool) for _ in range(3))
+    level = torch.empty(R, H, W, device=dev, dtype=torch.uint8) if dynamic else None
     stream = torch.cuda.current_stream(dev).cuda_stream
     pts, cols, counts = [], [], []
     for r0 in range(0, R, chunk):
@@ -288,12 +322,20 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if events is not None else None
         if marks:
             marks[0].record()
-        rc = lib.mvster_geo_scene_filter(depth.data_ptr(), conf.data_ptr(), p_pairs, p_ref, p_rm, p_vm,
-                                         mask_sum[r0:r1].data_ptr(), avg[r0:r1].data_ptr(), photo[r0:r1].data_ptr(),
-                                         geo[r0:r1].data_ptr(), final[r0:r1].data_ptr(), wg_counts.data_ptr(),
-                                         wg_offsets.data_ptr(), n, smax, V, H, W, float(conf_thres), int(thres_view),
-                                         float(pix_thres), float(rel_thres), stream)
-        _lib.check(rc, "geo_scene_filter")
+        if dynamic:
+            rc = lib.mvster_geo_scene_filter_dynamic(depth.data_ptr(), conf.data_ptr(), p_pairs, p_ref, p_rm, p_vm,
+                                                     mask_sum[r0:r1].data_ptr(), avg[r0:r1].data_ptr(),
+                                                     photo[r0:r1].data_ptr(), geo[r0:r1].data_ptr(), final[r0:r1].data_ptr(),
+                                                     level[r0:r1].data_ptr(), wg_counts.data_ptr(), wg_offsets.data_ptr(), n,
+                                                     smax, V, H, W, float(conf_thres), int(thres_view), float(pix_base),
+                                                     float(rel_base), stream)
+        else:
+            rc = lib.mvster_geo_scene_filter(depth.data_ptr(), conf.data_ptr(), p_pairs, p_ref, p_rm, p_vm,
+                                             mask_sum[r0:r1].data_ptr(), avg[r0:r1].data_ptr(), photo[r0:r1].data_ptr(),
+                                             geo[r0:r1].data_ptr(), final[r0:r1].data_ptr(), wg_counts.data_ptr(),
+                                             wg_offsets.data_ptr(), n, smax, V, H, W, float(conf_thres), int(thres_view),
+                                             float(pix_thres), float(rel_thres), stream)
+        _lib.check(rc, "geo_scene_filter_dynamic" if dynamic else "geo_scene_filter")
         if marks:
             marks[1].record()
         bounds = wg_offsets[::nblk].cpu()                                   # the one host sync: M and the per-view counts
@@ -312,17 +354,23 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
             events += [("filter+scan", marks[0], marks[1]), ("emit", marks[2], marks[3])]
         pts.append(points)
         cols.append(colors)
-    return SceneResult(points=pts[0] if len(pts) == 1 else torch.cat(pts), colors=cols[0] if len(cols) == 1 else torch.cat(cols),
-                       counts=torch.cat(counts).to(dev), photo_mask=photo, geo_mask=geo, final_mask=final,
-                       geo_mask_sum=mask_sum, depth_est_averaged=avg)
+    res = SceneResult(points=pts[0] if len(pts) == 1 else torch.cat(pts), colors=cols[0] if len(cols) == 1 else torch.cat(cols),
+                      counts=torch.cat(counts).to(dev), photo_mask=photo, geo_mask=geo, final_mask=final,
+                      geo_mask_sum=mask_sum, depth_est_averaged=avg)
+    if dynamic:
+        res["geo_level"] = level
+    return res
 
 
-def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, thres_view=5, device="cuda:0"):
+def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, thres_view=5, device="cuda:0",
+                 filter_method="normal", pix_base=PIX_BASE, rel_base=REL_BASE):
     """The reference's ``filter_depth`` (test_mvs4.py:331-421; its ``args.conf`` / ``args.thres_view`` are keywords
     here): reads ``pair_folder/pair.txt``, ``scan_folder/cams/{:0>8}_cam.txt`` and ``images/{:0>8}.jpg``,
     ``out_folder/depth_est/{:0>8}.pfm`` and ``confidence/{:0>8}.pfm`` -- every file once --, fuses the scan on the GPU and
     writes ``out_folder/mask/{:0>8}_{photo,geo,final}.png`` (:390-393) and the point cloud ``plyfilename``.
-    -> the vertex array."""
+    ``filter_method="dynamic"`` (with ``pix_base`` / ``rel_base``) writes the same files with the masks of dynamic
+    consistency checking, see ``fuse_scene``.  -> the vertex array."""
+    _check_method("filter_depth", filter_method)
     try:
         from PIL import Image
     except ImportError as e:
@@ -340,7 +388,8 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, th
     # 8-bit pixels as stored: (read_img's v / 255 * 255) truncated is v again, so the float image is never needed
     images = [np.array(Image.open(os.path.join(scan_folder, "images", name(v) + ".jpg")), dtype=np.uint8) for v in views]
     res = fuse_scene(depths, confs, images, [c[0] for c in cams], [c[1] for c in cams],
-                     [(slot[r], [slot[v] for v in srcs]) for r, srcs in pairs], conf, thres_view, device=device)
+                     [(slot[r], [slot[v] for v in srcs]) for r, srcs in pairs], conf, thres_view, device=device,
+                     method=filter_method, pix_base=pix_base, rel_base=rel_base)
     os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
     masks = {k: res[k + "_mask"].cpu().numpy() for k in ("photo", "geo", "final")}
     for i, (ref_view, _) in enumerate(pairs):

@@ -770,7 +770,7 @@ def write_scan_outputs(result, images, out_folder):
 
 
 def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres_view=5, plyfilename=None, short_sources=None,
-                     **kw):
+                     fusion="normal", pix_base=None, rel_base=None, **kw):
     """``infer_scan`` followed by ``fusion.fuse_scene`` on the device tensors: the reference's ``save_scene_depth`` +
     ``filter_depth`` (test_mvs4.py:170-268, :331-421) without leaving the GPU.  -> the ``fusion.SceneResult`` (with the
     ``ScanResult`` as its ``scan`` attribute); writes the point cloud to ``plyfilename`` if given.
@@ -781,8 +781,12 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     ``images/``), not from the
     re-encoded JPEGs the reference reads back from its output folder: positions and masks are the same, colours differ
     by the JPEG re-encoding the reference adds.  ``short_sources``: as ``infer_scan`` (fusion takes the pair lists as they
-    are, whatever their lengths)."""
-    from . import fusion
+    are, whatever their lengths).  ``fusion``: ``"normal"`` (the reference's fixed thresholds) or ``"dynamic"`` (dynamic
+    consistency checking with ``pix_base`` / ``rel_base``, ``fuse_scene``'s ``method``); none of the three reaches
+    ``infer_scan``."""
+    from . import fusion as fusion_mod
+    fusion_mod._check_method("reconstruct_scan", fusion)
+    bases = {k: v for k, v in (("pix_base", pix_base), ("rel_base", rel_base)) if v is not None}
     inp = plan_inputs(images, Ks, kw.get("max_h"), kw.get("max_w"), kw.get("crop_rows"), kw.get("img_wh"), Es)
     scan = infer_scan(model, inp.images, Ks, Es, depth_ranges, pairs, short_sources=short_sources, **kw)
     # (prepared: uint8 [V,Hd,Wd,3], already on the device; otherwise the input stack, which has the target size)
@@ -802,9 +806,9 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     if kind == "f32":
         img = img.permute(0, 2, 3, 1).contiguous()
     refs = np.asarray(scan["ref_views"])
-    res = fusion.fuse_scene(scan["depth"], scan["photometric_confidence"], img, scan["Ks"][refs], scan["Es"][refs], fpairs,
-                            conf, thres_view, device=dev)
+    res = fusion_mod.fuse_scene(scan["depth"], scan["photometric_confidence"], img, scan["Ks"][refs], scan["Es"][refs], fpairs,
+                                conf, thres_view, device=dev, method=fusion, **bases)
     res.scan = scan
     if plyfilename is not None:
-        fusion.write_ply(plyfilename, res.vertices())
+        fusion_mod.write_ply(plyfilename, res.vertices())
     return res
