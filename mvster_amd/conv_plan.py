@@ -596,7 +596,7 @@ class ConvLayer:
             None if self.prob is None else self.prob[0].data_ptr(), None if self.prob is None else self.prob[1].data_ptr(),
             out.data_ptr(), geom.ctypes.data_as(ctypes.c_void_p), int(geom.size), self.woff.ctypes.data_as(ctypes.c_void_p), self.cin,
             mt, nt, variant, ops._stream())
-        if rc == -3 and tiles is None and variant != 0:
+        if rc == _lib.ERR_UNSUPPORTED and tiles is None and variant != 0:
             # a heuristic (or stale table) choice the library has no instance for: the direct kernel takes every layer
             mt, nt = _tiles(B * geom[4] * geom[5] * geom[6], self.ntile_total, len(self.classes))
             rc = _lib.load().mvster_conv_mfma(

@@ -295,16 +295,9 @@ def warp_agg_fwd_cl(ref_cl, src_cl, rt, hypo, G, group_cor=True, attn_fuse_d=Tru
         raise RuntimeError("warp_agg_fwd: inconsistent shapes")
     out = torch.empty(B, D, h, w, G, device=ref_cl.device, dtype=torch.float32)
     wsum = torch.empty(B, D, h, w, device=ref_cl.device, dtype=torch.float32) if want_wsum else None
-    if nsrc is None:
-        rc = _lib.load().mvster_warp_agg_fwd(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), B, NV,
-                                             C, G, D, h, w, Hs, Ws, h * w * C, B * Hs * Ws * C, Hs * Ws * C,
-                                             int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant), _stream())
-    else:
-        nsrc = _source_counts(nsrc, NV, B, ref_cl.device, "warp_agg_fwd")
-        rc = _lib.load().mvster_warp_agg_fwd_counted(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum),
-                                                     B, NV, C, G, D, h, w, Hs, Ws, h * w * C, B * Hs * Ws * C, Hs * Ws * C,
-                                                     int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant),
-                                                     _ptr(nsrc), _stream())
+    args = (_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), B, NV, C, G, D, h, w, Hs, Ws, h * w * C,
+            B * Hs * Ws * C, Hs * Ws * C, int(group_cor), int(attn_fuse_d), float(attn_temp), int(variant))
+    rc, _ = _warp_agg_fwd_entry("warp_agg_fwd", args, nsrc, NV, B, ref_cl.device)
     _lib.check(rc, "warp_agg_fwd")
     return (out, wsum) if want_wsum else out
 
@@ -347,6 +340,15 @@ def _source_counts(nsrc, NV, B, device, what):
     return torch.from_numpy(check_source_counts(nsrc.numpy() if torch.is_tensor(nsrc) else nsrc, NV, B, what)).to(device)
 
 
+def _warp_agg_fwd_entry(name, args, nsrc, NV, B, device):
+    """The forward entry ``mvster_<name>(*args, stream)`` or, with source counts, ``mvster_<name>_counted(*args, nsrc, stream)``
+    -> (return code, the counts as the entry read them: device int32 [B], or None)."""
+    if nsrc is None:
+        return getattr(_lib.load(), "mvster_" + name)(*args, _stream()), None
+    nsrc = _source_counts(nsrc, NV, B, device, name)
+    return getattr(_lib.load(), "mvster_" + name + "_counted")(*args, _ptr(nsrc), _stream()), nsrc
+
+
 def warp_agg_fwd_indexed_cl(store, views, rt, hypo, G, group_cor=True, attn_fuse_d=True, attn_temp=2.0, want_wsum=False,
                             variant=0, nsrc=None):
     """``warp_agg_fwd_cl`` reading its maps from a level store: store [V,h,w,C] (one pyramid level of every view of a
@@ -374,18 +376,11 @@ def warp_agg_fwd_indexed_cl(store, views, rt, hypo, G, group_cor=True, attn_fuse
         raise RuntimeError("warp_agg_fwd_indexed: inconsistent shapes")
     out = torch.empty(B, D, h, w, G, device=store.device, dtype=torch.float32)
     wsum = torch.empty(B, D, h, w, device=store.device, dtype=torch.float32) if want_wsum else None
-    if nsrc is None:
-        rc = _lib.load().mvster_warp_agg_fwd_indexed(_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), V, B,
-                                                     NV, C, G, D, h, w, int(group_cor), int(attn_fuse_d), float(attn_temp),
-                                                     int(variant), _stream())
-    else:
-        nsrc = _source_counts(nsrc, NV, B, store.device, "warp_agg_fwd_indexed")
-        rc = _lib.load().mvster_warp_agg_fwd_indexed_counted(_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out),
-                                                             _ptr(wsum), V, B, NV, C, G, D, h, w, int(group_cor),
-                                                             int(attn_fuse_d), float(attn_temp), int(variant), _ptr(nsrc),
-                                                             _stream())
+    args = (_ptr(store), _ptr(views), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum), V, B, NV, C, G, D, h, w, int(group_cor),
+            int(attn_fuse_d), float(attn_temp), int(variant))
+    rc, nsrc = _warp_agg_fwd_entry("warp_agg_fwd_indexed", args, nsrc, NV, B, store.device)
     if rc == _lib.ERR_UNSUPPORTED:
-        # a kernel form that is not instantiated indexed (csrc/warp_agg.hip, kIndexedOneThread / kIndexedLanes), or no kernel
+        # a kernel form that is not instantiated indexed (csrc/warp_common.hpp, kIndexedOneThread / kIndexedLanes), or no kernel
         # at all: one gather launch into the view-major batch, then the plain entry -- which raises in the second case
         N = NV + 1
         maps = torch.empty(N, B, h, w, C, device=store.device, dtype=torch.float32)
@@ -471,12 +466,15 @@ def warp_agg_bwd_cl(ref_cl, src_cl, rt, hypo, out, wsum, grad_out, G, group_cor=
     if sorted_scatter is None:
         sorted_scatter = SORTED_SCATTER
     scratch = warp_agg_bwd_sorted_scratch(B, NV, C, D, h, w, Hs, Ws) if sorted_scatter else None
-    if scratch is not None:
-        g_ref, g_src = (torch.empty_like(ref_cl), torch.empty_like(src_cl)) if into is None else into
+    if into is not None:
+        g_ref, g_src = into
         if g_ref.shape != ref_cl.shape or g_src.shape != src_cl.shape:
             raise ValueError("warp_agg_bwd: `into` buffers must have the shapes of ref_cl and src_cl")
         _chk(g_ref, "warp_agg_bwd:into[0]")
         _chk(g_src, "warp_agg_bwd:into[1]")
+    if scratch is not None:
+        if into is None:
+            g_ref, g_src = torch.empty_like(ref_cl), torch.empty_like(src_cl)
         rec = torch.empty(scratch[0], device=ref_cl.device, dtype=torch.float32)
         ints = torch.empty(scratch[1], device=ref_cl.device, dtype=torch.int32)
         rc = lib.mvster_warp_agg_bwd_sorted(_ptr(ref_cl), _ptr(src_cl), _ptr(rt), _ptr(hypo), _ptr(out), _ptr(wsum),
@@ -486,14 +484,7 @@ def warp_agg_bwd_cl(ref_cl, src_cl, rt, hypo, out, wsum, grad_out, G, group_cor=
         _lib.check(rc, "warp_agg_bwd_sorted")
         return g_ref, g_src
     if into is None:
-        g_ref = torch.empty_like(ref_cl)
-        g_src = torch.zeros_like(src_cl)
-    else:
-        g_ref, g_src = into
-        if g_ref.shape != ref_cl.shape or g_src.shape != src_cl.shape:
-            raise ValueError("warp_agg_bwd: `into` buffers must have the shapes of ref_cl and src_cl")
-        _chk(g_ref, "warp_agg_bwd:into[0]")
-        _chk(g_src, "warp_agg_bwd:into[1]")
+        g_ref, g_src = torch.empty_like(ref_cl), torch.zeros_like(src_cl)
     if deterministic is None:
         deterministic = bool(os.environ.get("MVSTER_BWD_DETERMINISTIC"))
     nf, ni = ctypes.c_long(0), ctypes.c_long(0)
