@@ -505,7 +505,8 @@ int dispatch_wgrad_lds(const WgradArgs& a, int nblk, int cot, int cit, int packe
 #define MV_LP(M_, P_) if (mt == M_ && pcb == P_) return launch_wgrad_lds<M_, 1, TY, KW, P_>(a, nblk, cot, cit, s);
         const int ng8 = (TAPS + 1) / 2, ng4 = (TAPS + 3) / 4;
         int mt = cot;
-        while (mt > 1 && mt * (pcb == 8 ? ng8 : ng4) > wgrad_acc_limit()) mt /= 2;
+        // (5 M tiles -- 65 .. 80 outputs -- do not halve: 5 / 2 = 2 left cot / MT = 2 groups, rows 64 .. 79 of the slots unwritten)
+        while (mt > 1 && mt * (pcb == 8 ? ng8 : ng4) > wgrad_acc_limit()) mt = (mt & 1) ? 1 : mt / 2;
         MV_LP(1, 4) MV_LP(2, 4) MV_LP(4, 4) MV_LP(1, 8) MV_LP(2, 8) MV_LP(4, 8)
 #undef MV_LP
         return MVSTER_ERR_UNSUPPORTED;
