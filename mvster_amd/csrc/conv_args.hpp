@@ -1,6 +1,7 @@
 // Argument record and small helpers shared by the convolution kernels (conv_mfma.hip, conv_pers.hip).
 #pragma once
 #include "common.hpp"
+#include "conv_taps.h"
 
 namespace mvconv {
 
@@ -40,6 +41,7 @@ struct ConvArgs {
     // filled by the C entry point: multiply-shift division by Wo, Ho, Do (valid for dividends < 2^31)
     unsigned div_mul[3], div_shr[3];
     unsigned in_bytes;                                       // size of `in` (< 4 GB): buffer-load range check
+    mvtaps::TapDivs tapdiv[kMaxClasses];                     // ... and by kw, kh of each class (tap index -> kz, ky, kx)
 };
 
 __device__ __forceinline__ unsigned fast_div(unsigned n, unsigned d, unsigned mul, unsigned shr) {

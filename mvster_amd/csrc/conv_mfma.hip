@@ -27,6 +27,8 @@
 // (1,3,3) layers are HBM/L2-bound.  FLOPs per launch = 2 * M * Cout * taps * Cin.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "conv_args.hpp"
 
 namespace {
@@ -134,21 +136,20 @@ template <int CIN, int MT, int NT, bool SPLITK>
 __global__ void __launch_bounds__(256, conv_min_waves(MT, NT)) conv_mfma_kernel(ConvArgs a) {
     static_assert(CIN % 4 == 0 && (CIN >= 16 ? CIN % 16 == 0 : 16 % CIN == 0), "channel packing");
     __shared__ f32x4v red[SPLITK ? 3 * MT * NT * 64 : 1];
-    __shared__ int lut_ofs[kMaxTaps];   // linear input offset (voxels) of a tap
-    __shared__ int lut_zyx[kMaxTaps];   // kz | ky << 8 | kx << 16
 
+    // Everything the K loop needs to know about the class is wave-uniform and read once, here: the loop walks the taps in
+    // scalar registers (conv_taps.h), with no table in LDS and no barrier ahead of it.
     const int cls = blockIdx.z;
     const int KD = a.kd[cls], KH = a.kh[cls], KW = a.kw[cls];
+    const int PD = a.pd[cls], PH = a.ph[cls], PW = a.pw[cls];
     const int ntaps = KD * KH * KW;
-    for (int t = threadIdx.x; t < ntaps; t += blockDim.x) {
-        const int kx = t % KW, ky = (t / KW) % KH, kz = t / (KW * KH);
-        lut_ofs[t] = (kz * a.Hi + ky) * a.Wi + kx;
-        lut_zyx[t] = kz | (ky << 8) | (kx << 16);
-    }
-    __syncthreads();
+    const mvtaps::TapDivs tdv = a.tapdiv[cls];
+    const int nsteps_all = a.nsteps[cls];
+    const bool no_pad = a.all_inside[cls] != 0;   // 1x1-style classes: every tap of every voxel is inside
+    const bool fit = mvtaps::masks_fit(KD, KH, KW);
 
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // in a scalar register: so is every K step below
     const int lm = lane & 15;   // A row / B,D column
     const int lq = lane >> 4;   // K slot
     // all voxel counts fit 32 bits (checked on the host side of the ABI)
@@ -165,7 +166,8 @@ __global__ void __launch_bounds__(256, conv_min_waves(MT, NT)) conv_mfma_kernel(
     // A-role voxel of this lane in each M tile.  The same voxel is the one this lane stores in the
     // epilogue (swapped MFMA operands), so its output index is computed once, here.
     int iz0[MT], iy0[MT], ix0[MT];
-    int pin0[MT];
+    unsigned abase[MT];   // byte offset of the voxel's tap (0,0,0) (+ this lane's K slot when a step lies inside one tap)
+    unsigned vmask[MT];   // which kernel planes / rows / columns are inside the input for this voxel (conv_taps.h)
     int opix[MT];      // output voxel index, -1 = none
     int oyx[MT];       // oy << 16 | ox (for the upsample-add epilogue), b is opix / (DoF*HoF*WoF)
 #pragma unroll
@@ -179,10 +181,12 @@ __global__ void __launch_bounds__(256, conv_min_waves(MT, NT)) conv_mfma_kernel(
         const int y = (int)(r - r2 * (unsigned)a.Ho);
         const unsigned b = fast_div(r2, a.Do, a.div_mul[2], a.div_shr[2]);
         const int z = (int)(r2 - b * (unsigned)a.Do);
-        iz0[mt] = ok ? z * a.sd - a.pd[cls] : -(1 << 20);
-        iy0[mt] = y * a.sh - a.ph[cls];
-        ix0[mt] = x * a.sw - a.pw[cls];
-        pin0[mt] = (((int)b * a.Di + (ok ? iz0[mt] : 0)) * a.Hi + iy0[mt]) * a.Wi + ix0[mt];
+        iz0[mt] = ok ? z * a.sd - PD : -(1 << 20);      // a voxel past the end has no plane inside: every tap reads zeros
+        iy0[mt] = y * a.sh - PH;
+        ix0[mt] = x * a.sw - PW;
+        const int pin0 = (((int)b * a.Di + (ok ? iz0[mt] : 0)) * a.Hi + iy0[mt]) * a.Wi + ix0[mt];
+        abase[mt] = (unsigned)(pin0 * CIN + (CIN >= 16 ? lq * 4 : 0)) * 4u;
+        vmask[mt] = fit ? mvtaps::voxel_mask(iz0[mt], iy0[mt], ix0[mt], KD, KH, KW, a.Di, a.Hi, a.Wi) : 0u;
         const int oz = z * a.osd + a.od[cls], oy = y * a.osh + a.oh[cls], ox = x * a.osw + a.ow[cls];
         opix[mt] = ok ? (((int)b * a.DoF + oz) * a.HoF + oy) * a.WoF + ox : -1;
         oyx[mt] = (oy << 16) | ox;
@@ -194,42 +198,54 @@ __global__ void __launch_bounds__(256, conv_min_waves(MT, NT)) conv_mfma_kernel(
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4v){0.f, 0.f, 0.f, 0.f};
 
-    const float* wp = a.wpk + a.woff[cls] + ((long)nt0 * 64 + lane) * 4;
-    const long wstep = (long)a.ntile_total * 256;
-    const int nsteps_all = a.nsteps[cls];
-    // K steps of this wave: first, first+stride, ... (all of them unless SPLITK)
-    const int kfirst = SPLITK ? wave : 0, kstride = SPLITK ? 4 : 1;
-    const int nsteps = SPLITK ? (nsteps_all - wave + 3) / 4 : nsteps_all;
+    // Weights: one descriptor per class and N-tile group; the K step goes in as the scalar offset, the N tile as the
+    // immediate one, and the lane's constant 16 bytes of the fragment are the only vector part.
+    const long wstep = (long)a.ntile_total * 1024;      // bytes per K step
+    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.wpk + a.woff[cls] + (long)nt0 * 256), (short)0,
+        (int)((unsigned)nsteps_all * (unsigned)wstep - (unsigned)nt0 * 1024u), 0x00020000);
+    const unsigned wlane = (unsigned)lane * 16u;
 
     // Activations are read through a buffer descriptor: the offset of a padded tap is pushed past the
     // end of the tensor and the hardware range check returns zeros -- no branch, no select on the data,
-    // 32-bit address arithmetic only.
+    // 32-bit address arithmetic only.  (The sentinel has to be in the VECTOR offset: the range check does not see
+    // the scalar one.)
     const __amdgpu_buffer_rsrc_t in_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), (short)0, (int)a.in_bytes, 0x00020000);
-    const bool no_pad = a.all_inside[cls] != 0;   // 1x1-style classes: every tap of every voxel is inside
-    f32x4v af[MT], bf[NT];
-    auto load_step = [&](int si, f32x4v (&A)[MT], f32x4v (&Bv)[NT]) {
-        const int s = kfirst + si * kstride;
-        const int kk = s * 16 + lq * 4;
-        const int tap = kk / CIN;
-        const int c = kk % CIN;
-        const bool tap_ok = tap < ntaps;
-        const int tt = tap_ok ? tap : 0;
-        const int ofs = lut_ofs[tt];
-        const int zyx = lut_zyx[tt];
-        const int kz = zyx & 255, ky = (zyx >> 8) & 255, kx = zyx >> 16;
+    const int nsteps = mvtaps::wave_steps(nsteps_all, wave, SPLITK);
+
+    // One K step's operands.  MODE 0: a class without padding whose step lies inside one tap -- the lane's offset never
+    // changes, the tap's goes in as the scalar offset (a voxel past the end reads voxel 0's taps into rows that are
+    // never stored).  MODE 1: one bit test against the voxel's mask, one add, one select.  MODE 2: kernels too wide for
+    // the mask compare each axis.  For CIN >= 16 the tap, its offset and its mask bits are scalars; for CIN 4 / 8 the
+    // K slot picks the tap and the same expressions are per lane.
+    auto uni = [](unsigned v) { return CIN >= 16 ? (unsigned)__builtin_amdgcn_readfirstlane((int)v) : v; };
+    auto load_step = [&](auto mode, int si, f32x4v (&A)[MT], f32x4v (&Bv)[NT]) {
+        constexpr int MODE = decltype(mode)::value;
+        const int s = mvtaps::wave_step(si, wave, SPLITK);
+        const int tap = mvtaps::step_tap<CIN>(s, lq);
+        const int c = CIN >= 16 ? s * 16 - tap * CIN : mvtaps::step_channel<CIN>(s, lq);
+        const bool tap_ok = CIN >= 16 || tap < ntaps;      // (CIN >= 16: nsteps * 16 = ntaps * CIN exactly)
+        const mvtaps::Tap t = mvtaps::tap_decode(tap_ok ? tap : 0, KH, KW, tdv);
+        // (uni: pinned to scalar registers where the step lies inside one tap -- and so computed for every step, not
+        //  under a branch on the lanes that need it)
+        const unsigned uoff = uni((unsigned)(mvtaps::tap_offset(t, a.Hi, a.Wi) * CIN + c) * 4u);
+        const unsigned sel = MODE == 1 ? uni(mvtaps::tap_select(t, KD, KH)) : 0u;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            bool ok = tap_ok && iz0[mt] > -(1 << 19);
-            if (!no_pad)
-                ok = ok && (unsigned)(iz0[mt] + kz) < (unsigned)a.Di && (unsigned)(iy0[mt] + ky) < (unsigned)a.Hi &&
-                     (unsigned)(ix0[mt] + kx) < (unsigned)a.Wi;
-            const unsigned off = ok ? (unsigned)((pin0[mt] + ofs) * CIN + c) * 4u : 0xFFFFFFF0u;
-            A[mt] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0));
+            if constexpr (MODE == 0) {
+                A[mt] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, abase[mt], uoff, 0));
+            } else {
+                const bool ok = tap_ok && (MODE == 1 ? mvtaps::tap_inside(vmask[mt], sel)
+                                                     : mvtaps::tap_inside_cmp(iz0[mt], iy0[mt], ix0[mt], t, a.Di, a.Hi, a.Wi));
+                const unsigned off = ok ? abase[mt] + uoff : 0xFFFFFFF0u;
+                A[mt] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0));
+            }
         }
+        const unsigned woff = (unsigned)s * (unsigned)wstep;      // (SPLITK or not, s is a scalar)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-            Bv[nt] = *reinterpret_cast<const f32x4v*>(wp + (long)s * wstep + (long)nt * 256);
+            Bv[nt] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wlane + nt * 1024u, woff, 0));
     };
 
     auto mma_step = [&](const f32x4v (&A)[MT], const f32x4v (&Bv)[NT]) {
@@ -245,17 +261,33 @@ __global__ void __launch_bounds__(256, conv_min_waves(MT, NT)) conv_mfma_kernel(
     // Two register sets, ping-pong: the loads of step s+1 are in flight under the MFMAs of step s.
     // Every prefetch is unconditional (the last one re-reads the final step) so that hipcc can
     // count the outstanding loads exactly (a conditional prefetch makes it wait vmcnt(0)).
-    f32x4v ag[MT], bg[NT];
-    if (nsteps > 0) {
-        load_step(0, af, bf);
+    // (Three sets, two steps ahead, at MT * NT <= 2: no wave lost, and slower -- 160.5 against 155.2 us summed over the
+    //  forward's 18 launches; the address phase was what the MFMAs waited for, not the operand latency.)
+    auto k_loop = [&](auto mode) {
+        f32x4v af[MT], bf[NT], ag[MT], bg[NT];
+        if (nsteps <= 0) return;
+        const int last = nsteps - 1;
+        load_step(mode, 0, af, bf);
         int s = 0;
         for (; s + 2 <= nsteps; s += 2) {
-            load_step(s + 1, ag, bg);
+            load_step(mode, s + 1, ag, bg);
             mma_step(af, bf);
-            load_step(s + 2 < nsteps ? s + 2 : nsteps - 1, af, bf);
+            load_step(mode, min(s + 2, last), af, bf);
             mma_step(ag, bg);
         }
         if (s < nsteps) mma_step(af, bf);
+    };
+    if (!fit) {
+        // kernels of more than 32 planes + rows + columns (none in the network): one step at a time
+        f32x4v af[MT], bf[NT];
+        for (int s = 0; s < nsteps; ++s) {
+            load_step(std::integral_constant<int, 2>{}, s, af, bf);
+            mma_step(af, bf);
+        }
+    } else if (CIN >= 16 && no_pad) {
+        k_loop(std::integral_constant<int, CIN >= 16 ? 0 : 1>{});
+    } else {
+        k_loop(std::integral_constant<int, 1>{});
     }
 
     if (SPLITK) {
@@ -645,6 +677,8 @@ extern "C" int mvster_conv_mfma(const float* in, const float* wpk, const float* 
         a.nsteps[c] = geom[i++];
         a.woff[c] = woff[c];
         if (a.kd[c] * a.kh[c] * a.kw[c] > kMaxTaps || a.nsteps[c] < 1) return MVSTER_ERR_SHAPE;
+        if (a.kd[c] < 1 || a.kh[c] < 1 || a.kw[c] < 1) return MVSTER_ERR_SHAPE;
+        a.tapdiv[c] = mvtaps::make_tap_divs(a.kh[c], a.kw[c]);
     }
     if (a.B <= 0 || a.Do <= 0 || a.Ho <= 0 || a.Wo <= 0 || a.cout <= 0 || a.ntile_total <= 0) return MVSTER_ERR_SHAPE;
     find_divisor((unsigned)a.Wo, a.div_mul[0], a.div_shr[0]);
