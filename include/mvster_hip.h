@@ -559,6 +559,35 @@ int mvster_fused_adam(const void* const* params, const void* const* grads, const
  * from their parameters after an optimizer update (host-side plumbing: the reference's layers read the parameters directly). */
 int mvster_gather_batch(const void* descs, int ndesc, int total_blocks, void* stream);
 
+/* ---- voxel-grid thinning of a fused cloud (csrc/geo_thin.hip, csrc/voxel_math.h) ---- */
+
+/* Workgroups (= leader counts) for a cloud of M points: the length of wg_counts; wg_offsets holds three more.
+ * MVSTER_ERR_SHAPE for M <= 0 or M > 2^29 (a slot index and its leader mark share 32 bits). */
+int mvster_voxel_thin_blocks(long M);
+
+/* Insert + leaders + scan.  points [M,3] float32; voxel = the edge v, finite and > 0.  Per point and axis, in fp64:
+ * q = p / v, i = floor(q); a point is valid iff -2^20 <= i < 2^20 on all axes; its voxel key is ((ix + 2^20) << 42) |
+ * ((iy + 2^20) << 21) | (iz + 2^20).  keys [table_slots] uint64 / first [table_slots] int32 (scratch) = the open-addressing
+ * table, filled here by a kernel; table_slots a power of two, >= 64, >= 2 * M, <= 2^30 -- anything else is
+ * MVSTER_ERR_SHAPE before any launch.  slot [M] int32 (scratch): a point's slot, -2 - slot for the first point of a
+ * voxel, -1 for an invalid point.  wg_counts [blocks] int32 (scratch); wg_offsets [blocks + 3] int64 = the exclusive scan
+ * of the first points per workgroup, then U = occupied voxels, dropped = invalid points, status (non-zero: a point found
+ * no slot, which a legal table_slots excludes) -- three neighbouring words, the caller's one read-back.  Four launches; the
+ * probe loop runs at most table_slots iterations. */
+int mvster_voxel_thin_insert(const float* points, long M, float voxel, unsigned long long* keys, int* first, long table_slots,
+                             int* slot, int* wg_counts, long* wg_offsets, void* stream);
+
+/* Rank + accumulate + emit, with first / slot / wg_offsets as mvster_voxel_thin_insert left them (first is overwritten by
+ * ranks) and U read back by the caller.  Voxels in the order of their first point f: out_first [U] int64 = f, out_counts
+ * [U] int32 = n, the voxel's valid points.  reduce 1 ("first"): out_points / out_colors = point f and its colour, bits
+ * unchanged; sums may be NULL.  reduce 0 ("mean"): with t = min((int64)floor((q - i) * 65536), 65535) per point and axis,
+ * S their sums and C the colour sums (sums [U,6] uint64, scratch), out_points = (float)((i + (S + 0.5 n) / (65536 n)) * v)
+ * in fp64, out_colors = (2 C + n) / (2 n) in integers (round half up).  Integer atomics only: bit-reproducible.  U = 0
+ * launches nothing; another reduce is MVSTER_ERR_UNSUPPORTED.  Four launches. */
+int mvster_voxel_thin_emit(const float* points, const unsigned char* colors, long M, float voxel, int reduce, int* first,
+                           const int* slot, const long* wg_offsets, unsigned long long* sums, float* out_points,
+                           unsigned char* out_colors, int* out_counts, long* out_first, long U, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

@@ -89,6 +89,9 @@ SIGNATURES = {
     "mvster_geo_scene_filter": [_f] * 13 + [_i] * 5 + [_fl, _i, _fl, _fl, _f],
     "mvster_geo_scene_filter_dynamic": [_f] * 14 + [_i] * 5 + [_fl, _i, _fl, _fl, _f],
     "mvster_geo_scene_emit": [_f] * 5 + [_i, _f, _f, _f, _l, _i, _i, _i, _i, _f],
+    "mvster_voxel_thin_blocks": [_l],
+    "mvster_voxel_thin_insert": [_f, _l, _fl, _f, _f, _l, _f, _f, _f, _f],
+    "mvster_voxel_thin_emit": [_f, _f, _l, _fl, _i] + [_f] * 8 + [_l, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

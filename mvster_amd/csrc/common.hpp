@@ -18,6 +18,9 @@ static inline int mv_check_launch() {
     return e == hipSuccess ? MVSTER_OK : MVSTER_ERR_LAUNCH;
 }
 
+// offsets[i] = sum(counts[0..i)), i = 0..n, one single-workgroup launch (geo_scene.hip; geo_thin.hip scans with it too)
+int mv_scan_counts(const int* counts, long* offsets, long n, hipStream_t stream);
+
 // What the last launcher called on this host thread dispatched, spelled like the profiler spells the kernel
 // ("conv_lds_kernel<2, 1, 3, 1, 3>"): mvster_last_kernel() hands it to the caller, so that bench.py attributes its
 // event timings to the kernel the library really chose instead of re-deriving the dispatch rules.

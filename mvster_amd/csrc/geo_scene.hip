@@ -242,6 +242,11 @@ long scene_blocks(int R, int H, int W) { return (long)R * (((long)H * W + kWG - 
 
 }  // namespace
 
+int mv_scan_counts(const int* counts, long* offsets, long n, hipStream_t stream) {
+    hipLaunchKernelGGL(geo_scene_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, counts, offsets, n);
+    return mv_check_launch();
+}
+
 extern "C" int mvster_geo_scene_blocks(int R, int H, int W) {
     if (R <= 0 || H <= 0 || W <= 0) return MVSTER_ERR_SHAPE;
     const long n = scene_blocks(R, H, W);
@@ -268,9 +273,7 @@ extern "C" int mvster_geo_scene_filter(const float* depth, const float* confiden
     hipLaunchKernelGGL(geo_scene_filter_kernel, dim3((unsigned)nwg), dim3(kWG), 0, (hipStream_t)stream, a);
     int rc = mv_check_launch();
     if (rc != MVSTER_OK) return rc;
-    hipLaunchKernelGGL(geo_scene_scan_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, wg_counts, wg_offsets,
-                       (long)nwg);
-    return mv_check_launch();
+    return mv_scan_counts(wg_counts, wg_offsets, (long)nwg, (hipStream_t)stream);
 }
 
 extern "C" int mvster_geo_scene_filter_dynamic(const float* depth, const float* confidence, const int* pairs,
@@ -300,9 +303,7 @@ extern "C" int mvster_geo_scene_filter_dynamic(const float* depth, const float* 
     hipLaunchKernelGGL(geo_scene_dynamic_filter_kernel, dim3((unsigned)nwg), dim3(kWG), 0, (hipStream_t)stream, d);
     int rc = mv_check_launch();
     if (rc != MVSTER_OK) return rc;
-    hipLaunchKernelGGL(geo_scene_scan_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream, wg_counts, wg_offsets,
-                       (long)nwg);
-    return mv_check_launch();
+    return mv_scan_counts(wg_counts, wg_offsets, (long)nwg, (hipStream_t)stream);
 }
 
 extern "C" int mvster_geo_scene_emit(const double* depth_avg, const unsigned char* final_mask, const int* ref_view,

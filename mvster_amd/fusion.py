@@ -200,9 +200,13 @@ class SceneResult(dict):
     ``geo_mask``, ``final_mask``, ``geo_mask_sum``, ``depth_est_averaged``; with ``method="dynamic"`` also ``geo_level``)
     plus ``vertices()``."""
 
-    def vertices(self):
-        """The structured vertex array of filter_depth (test_mvs4.py:409-418) on the host, ready for ``write_ply``."""
-        pts, cols = self["points"].cpu().numpy(), self["colors"].cpu().numpy()
+    def vertices(self, thinned=False):
+        """The structured vertex array of filter_depth (test_mvs4.py:409-418) on the host, ready for ``write_ply``;
+        ``thinned``: of the voxel-thinned cloud (``fuse_scene(voxel_size=...)``), an error if there is none."""
+        if thinned and "thin_points" not in self:
+            raise RuntimeError("SceneResult.vertices(thinned=True): this result holds no thinned cloud (fuse_scene was "
+                               "called without voxel_size)")
+        pts, cols = (self[("thin_" if thinned else "") + k].cpu().numpy() for k in ("points", "colors"))
         v = np.empty(len(pts), dtype=PLY_VERTEX_DTYPE)
         v["x"], v["y"], v["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
         v["red"], v["green"], v["blue"] = cols[:, 0], cols[:, 1], cols[:, 2]
@@ -238,9 +242,103 @@ def _check_method(what, method, pix_thres=None, rel_thres=None):
                            "pix_base / rel_base" % what)
 
 
+VOXEL_REDUCE = ("mean", "first")
+MAX_THIN_POINTS = 1 << 29               # a slot index and its leader mark share 32 bits (mvster_voxel_thin_blocks)
+
+
+def _check_voxel(what, voxel_size, voxel_reduce):
+    """voxel_size None (no thinning) or a number whose float32 value is finite and > 0; voxel_reduce one of VOXEL_REDUCE."""
+    if voxel_reduce not in VOXEL_REDUCE:
+        raise RuntimeError("%s: unknown voxel reduction %r (one of %s)" % (what, voxel_reduce, ", ".join(VOXEL_REDUCE)))
+    if voxel_size is None:
+        return None
+    try:
+        with np.errstate(over="ignore"):
+            v = float(np.float32(voxel_size))
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: voxel_size must be a number, not %r" % (what, voxel_size)) from None
+    if not (np.isfinite(v) and v > 0):
+        raise RuntimeError("%s: voxel_size must be finite and > 0 as a float32, not %r" % (what, voxel_size))
+    return v
+
+
+def thin_slots(M):
+    """The table size ``thin_points`` uses for M points: the smallest power of two >= 2 * M, at least 64."""
+    return max(64, 1 << max(0, 2 * int(M) - 1).bit_length())
+
+
+def thin_points(points, colors, voxel_size, reduce="mean", table_slots=None):
+    """Voxel-grid thinning of a cloud on the GPU (what Open3D and PCL call voxel_down_sample, defined
+    exactly in mvster_amd/csrc/voxel_math.h): ``points`` [M,3] float32 and ``colors`` [M,3] uint8 tensors on the GPU, one
+    output point per occupied voxel of edge ``voxel_size`` (its float32 value; finite, > 0).  ``reduce="first"`` keeps each
+    voxel's first input point and colour as they are, ``"mean"`` gives the mean of the voxel's points (16-bit fixed-point
+    offsets inside the voxel, integer sums) and the mean colour rounded half up.  Voxels come in the order of their first
+    point, so the thinned cloud keeps the input's order.  Points with a NaN or infinite coordinate, or beyond 2^20 voxels from
+    the origin on an axis, take no part.  -> dict: ``points`` [U,3] float32, ``colors`` [U,3] uint8, ``counts`` [U] int32
+    (points per voxel), ``first`` [U] int64 (index of each voxel's first point: gathers any other per-point attribute) on the
+    GPU, ``dropped`` (int) = the points that took no part.  Integer atomics only: two runs give the same bytes.  One host
+    synchronisation (U and ``dropped`` in one copy).  ``table_slots``: size of the hash table, a power of two >= max(64,
+    2 * M) (default: the smallest); the result does not depend on it.  No CPU fallback."""
+    v = _check_voxel("thin_points", voxel_size, reduce)
+    if v is None:
+        raise RuntimeError("thin_points: voxel_size must be finite and > 0 as a float32, not None")
+    if not isinstance(points, torch.Tensor) or not isinstance(colors, torch.Tensor):
+        raise RuntimeError("thin_points: points and colors must be torch tensors (on the GPU)")
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise RuntimeError("thin_points: points must be [M,3] float32, not %s %s" % (tuple(points.shape), points.dtype))
+    if tuple(colors.shape) != tuple(points.shape) or colors.dtype != torch.uint8:
+        raise RuntimeError("thin_points: colors must be [M,3] uint8 with the M of points (%d), not %s %s" %
+                           (points.shape[0], tuple(colors.shape), colors.dtype))
+    M = points.shape[0]
+    if M > MAX_THIN_POINTS:
+        raise RuntimeError("thin_points: at most 2^29 points, not %d" % M)
+    slots = thin_slots(M) if table_slots is None else table_slots
+    if not isinstance(slots, int) or slots < thin_slots(M) or slots & (slots - 1) or slots > 1 << 30:
+        raise RuntimeError("thin_points: table_slots must be a power of two, >= max(64, 2 * M) = %d and <= 2^30, not %r" %
+                           (max(64, 2 * M), table_slots))
+    if not points.is_cuda or colors.device != points.device:
+        raise RuntimeError("mvster_amd.fusion.thin_points runs on MI355X only: points and colors must be tensors on one GPU "
+                           "(there is no CPU fallback)")
+    dev = points.device
+    empty = dict(points=torch.empty(0, 3, device=dev, dtype=torch.float32), colors=torch.empty(0, 3, device=dev, dtype=torch.uint8),
+                 counts=torch.empty(0, device=dev, dtype=torch.int32), first=torch.empty(0, device=dev, dtype=torch.int64))
+    if M == 0:
+        return dict(empty, dropped=0)
+    points, colors = points.contiguous(), colors.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        nblk = lib.mvster_voxel_thin_blocks(M)
+        _lib.check(min(nblk, 0), "voxel_thin_blocks")
+        keys = torch.empty(slots, device=dev, dtype=torch.int64)
+        first = torch.empty(slots, device=dev, dtype=torch.int32)
+        slot = torch.empty(M, device=dev, dtype=torch.int32)
+        wg_counts = torch.empty(nblk, device=dev, dtype=torch.int32)
+        wg_offsets = torch.empty(nblk + 3, device=dev, dtype=torch.int64)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mvster_voxel_thin_insert(points.data_ptr(), M, v, keys.data_ptr(), first.data_ptr(), slots, slot.data_ptr(),
+                                          wg_counts.data_ptr(), wg_offsets.data_ptr(), stream)
+        _lib.check(rc, "voxel_thin_insert")
+        U, dropped, status = wg_offsets[nblk:].tolist()                      # the one host sync
+        if status:
+            raise RuntimeError("thin_points: a point found no slot in a table of %d slots for %d points" % (slots, M))
+        if U == 0:
+            return dict(empty, dropped=dropped)
+        del keys
+        mean = reduce == "mean"
+        out = dict(points=torch.empty(U, 3, device=dev, dtype=torch.float32), colors=torch.empty(U, 3, device=dev, dtype=torch.uint8),
+                   counts=torch.empty(U, device=dev, dtype=torch.int32), first=torch.empty(U, device=dev, dtype=torch.int64))
+        sums = torch.empty(U, 6, device=dev, dtype=torch.int64) if mean else None
+        rc = lib.mvster_voxel_thin_emit(points.data_ptr(), colors.data_ptr(), M, v, 0 if mean else 1, first.data_ptr(),
+                                        slot.data_ptr(), wg_offsets.data_ptr(), sums.data_ptr() if mean else None,
+                                        out["points"].data_ptr(), out["colors"].data_ptr(), out["counts"].data_ptr(),
+                                        out["first"].data_ptr(), U, stream)
+        _lib.check(rc, "voxel_thin_emit")
+    return dict(out, dropped=dropped)
+
+
 def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=None, rel_thres=None,
                device=None, scratch_budget=SCRATCH_BUDGET, events=None, method="normal", pix_base=PIX_BASE,
-               rel_base=REL_BASE):
+               rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean"):
     """filter_depth (test_mvs4.py:331-421) for a scan whose maps are in memory.  depths / confidences [V,H,W], images
     [V,H,W,3] (uint8, or float 0..1 as ``read_img`` returns it), Ks [V,3,3], Es [V,4,4]: NumPy arrays, tensors or
     sequences of them, indexed by the view numbers in ``pairs`` [(ref_view, [src_view, ...]), ...].  Tensors already on
@@ -258,8 +356,13 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     sources agree within n * ``pix_base`` pixels and n * ``rel_base`` relative depth; the result then also holds
     ``geo_level`` [R,H,W] uint8, that n (0 = none), ``geo_mask_sum`` counts the sources agreeing at the loosest level and
     ``depth_est_averaged`` averages over them.  At most 32 sources per reference view; ``pix_thres`` / ``rel_thres``
-    belong to ``"normal"`` and may not be given."""
+    belong to ``"normal"`` and may not be given.
+
+    ``voxel_size`` (default None: nothing changes): the whole cloud, after its chunks are joined, also goes through
+    ``thin_points(points, colors, voxel_size, voxel_reduce)`` and the result holds ``thin_points``, ``thin_colors``,
+    ``thin_counts``, ``thin_first`` and ``thin_dropped`` beside the unchanged ``points``, ``colors`` and ``counts``."""
     _check_method("fuse_scene", method, pix_thres, rel_thres)
+    _check_voxel("fuse_scene", voxel_size, voxel_reduce)
     dynamic = method == "dynamic"
     pix_thres = PIX_THRES if pix_thres is None else pix_thres
     rel_thres = REL_THRES if rel_thres is None else rel_thres
@@ -359,18 +462,22 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
                       geo_mask_sum=mask_sum, depth_est_averaged=avg)
     if dynamic:
         res["geo_level"] = level
+    if voxel_size is not None:
+        res.update(("thin_" + k, t) for k, t in thin_points(res["points"], res["colors"], voxel_size, voxel_reduce).items())
     return res
 
 
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, thres_view=5, device="cuda:0",
-                 filter_method="normal", pix_base=PIX_BASE, rel_base=REL_BASE):
+                 filter_method="normal", pix_base=PIX_BASE, rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean"):
     """The reference's ``filter_depth`` (test_mvs4.py:331-421; its ``args.conf`` / ``args.thres_view`` are keywords
     here): reads ``pair_folder/pair.txt``, ``scan_folder/cams/{:0>8}_cam.txt`` and ``images/{:0>8}.jpg``,
     ``out_folder/depth_est/{:0>8}.pfm`` and ``confidence/{:0>8}.pfm`` -- every file once --, fuses the scan on the GPU and
     writes ``out_folder/mask/{:0>8}_{photo,geo,final}.png`` (:390-393) and the point cloud ``plyfilename``.
     ``filter_method="dynamic"`` (with ``pix_base`` / ``rel_base``) writes the same files with the masks of dynamic
-    consistency checking, see ``fuse_scene``.  -> the vertex array."""
+    consistency checking, see ``fuse_scene``.  With ``voxel_size`` the cloud written and returned is the voxel-thinned one
+    (``thin_points`` with ``voxel_reduce``).  -> the vertex array."""
     _check_method("filter_depth", filter_method)
+    _check_voxel("filter_depth", voxel_size, voxel_reduce)
     try:
         from PIL import Image
     except ImportError as e:
@@ -389,12 +496,13 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, th
     images = [np.array(Image.open(os.path.join(scan_folder, "images", name(v) + ".jpg")), dtype=np.uint8) for v in views]
     res = fuse_scene(depths, confs, images, [c[0] for c in cams], [c[1] for c in cams],
                      [(slot[r], [slot[v] for v in srcs]) for r, srcs in pairs], conf, thres_view, device=device,
-                     method=filter_method, pix_base=pix_base, rel_base=rel_base)
+                     method=filter_method, pix_base=pix_base, rel_base=rel_base, voxel_size=voxel_size,
+                     voxel_reduce=voxel_reduce)
     os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
     masks = {k: res[k + "_mask"].cpu().numpy() for k in ("photo", "geo", "final")}
     for i, (ref_view, _) in enumerate(pairs):
         for k, m in masks.items():                                          # save_mask: bool -> uint8 * 255
             Image.fromarray(m[i].astype(np.uint8) * 255).save(os.path.join(out_folder, "mask", name(ref_view) + "_%s.png" % k))
-    vertices = res.vertices()
+    vertices = res.vertices(thinned=voxel_size is not None)
     write_ply(plyfilename, vertices)
     return vertices

@@ -770,7 +770,7 @@ def write_scan_outputs(result, images, out_folder):
 
 
 def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres_view=5, plyfilename=None, short_sources=None,
-                     fusion="normal", pix_base=None, rel_base=None, **kw):
+                     fusion="normal", pix_base=None, rel_base=None, voxel_size=None, voxel_reduce="mean", **kw):
     """``infer_scan`` followed by ``fusion.fuse_scene`` on the device tensors: the reference's ``save_scene_depth`` +
     ``filter_depth`` (test_mvs4.py:170-268, :331-421) without leaving the GPU.  -> the ``fusion.SceneResult`` (with the
     ``ScanResult`` as its ``scan`` attribute); writes the point cloud to ``plyfilename`` if given.
@@ -783,9 +783,11 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     by the JPEG re-encoding the reference adds.  ``short_sources``: as ``infer_scan`` (fusion takes the pair lists as they
     are, whatever their lengths).  ``fusion``: ``"normal"`` (the reference's fixed thresholds) or ``"dynamic"`` (dynamic
     consistency checking with ``pix_base`` / ``rel_base``, ``fuse_scene``'s ``method``); none of the three reaches
-    ``infer_scan``."""
+    ``infer_scan``.  ``voxel_size`` / ``voxel_reduce``: as ``fuse_scene`` (named keywords, they do not reach ``infer_scan``
+    either); with a ``voxel_size`` the result also holds the ``thin_*`` cloud and that is the one written to ``plyfilename``."""
     from . import fusion as fusion_mod
     fusion_mod._check_method("reconstruct_scan", fusion)
+    fusion_mod._check_voxel("reconstruct_scan", voxel_size, voxel_reduce)
     bases = {k: v for k, v in (("pix_base", pix_base), ("rel_base", rel_base)) if v is not None}
     inp = plan_inputs(images, Ks, kw.get("max_h"), kw.get("max_w"), kw.get("crop_rows"), kw.get("img_wh"), Es)
     scan = infer_scan(model, inp.images, Ks, Es, depth_ranges, pairs, short_sources=short_sources, **kw)
@@ -807,8 +809,9 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
         img = img.permute(0, 2, 3, 1).contiguous()
     refs = np.asarray(scan["ref_views"])
     res = fusion_mod.fuse_scene(scan["depth"], scan["photometric_confidence"], img, scan["Ks"][refs], scan["Es"][refs], fpairs,
-                                conf, thres_view, device=dev, method=fusion, **bases)
+                                conf, thres_view, device=dev, method=fusion, voxel_size=voxel_size,
+                                voxel_reduce=voxel_reduce, **bases)
     res.scan = scan
     if plyfilename is not None:
-        fusion_mod.write_ply(plyfilename, res.vertices())
+        fusion_mod.write_ply(plyfilename, res.vertices(thinned=voxel_size is not None))
     return res
