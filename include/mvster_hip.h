@@ -256,6 +256,17 @@ int mvster_conv_narrow_pair(const float* in, const float* w1, const float* scale
                             const float* scale2, const float* shift2, float* out, int NB, int H, int W, int relu1, int relu2,
                             int wpc, void* stream);
 
+/* mvster_pack_images + mvster_conv_narrow_pair in one launch, without the RGB0 copy: the loading waves read the planes of
+ * imgs (N <= 8 views, each a contiguous [B,3,H,W] block, 4-byte aligned) themselves -> out [N*B,H,W,8] (batch index v*B+b),
+ * bit for bit.  With proj_matrices non-null the launch also does the two small jobs of mvster_forward_prologue (same
+ * arguments and bits): rt [nstage,B,N-1,12] and the first stage's hypotheses hypo [B,D,h,w], in a few workgroups dispatched
+ * ahead of the tiles; with proj_matrices null the arguments from nstage to inverse are ignored. */
+int mvster_conv_narrow_pair_planes(const float* const* imgs, int N, int B, int H, int W, const float* w1, const float* scale1,
+                                   const float* shift1, const float* w2, const float* scale2, const float* shift2, float* out,
+                                   int relu1, int relu2, int wpc, const float* const* proj_matrices, int nstage, float* rt,
+                                   const float* depth_values, int ndv, float* hypo, int D, int h, int w, int inverse,
+                                   void* stream);
+
 /* ConvTranspose3d (1,3,3), stride (1,2,2), padding (0,1,1), output_padding (0,1,1) + BatchNorm scale/shift +
  * ReLU + skip add for (cin, cout) in {(16,8), (32,16)} on the VALU (the layers are HBM-bound).  in [NB,Hi,Wi,cin],
  * w [3,3,cin,cout], skip optional [NB,2Hi,2Wi,cout]; prob_w/prob_b optional (cout == 8): fuse the 1x1x1 head,
@@ -273,6 +284,16 @@ int mvster_deconv_select(const float* in, const float* w, const float* scale, co
                          const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth, float* conf,
                          float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi, int Wi, int cin, int relu,
                          float split_itv, void* stream);
+
+/* mvster_deconv_select followed by mvster_upsample_bilinear_multi, bit for bit, in one launch: workgroups behind the
+ * selection's own interpolate up_ins[k] [B,up_his[k],up_wis[k]] -> up_outs[k] [B,ho,wo], k < n <= 3.  The maps must be
+ * complete before the launch (the coarse stages' confidence maps at the last stage).  D in {4, 8}; any other D returns
+ * MVSTER_ERR_UNSUPPORTED and launches nothing. */
+int mvster_deconv_select_riders(const float* in, const float* w, const float* scale, const float* shift, const float* skip,
+                                const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth,
+                                float* conf, float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi, int Wi,
+                                int cin, int relu, float split_itv, const float* const* up_ins, float* const* up_outs,
+                                const int* up_his, const int* up_wis, int n, int ho, int wo, void* stream);
 
 /* FPN4 top-down tail, re-associated: G [NB,H/2,W/2,9*CO] = 1x1 conv of the half-resolution top-down
  * map with the 9 taps of the output conv stacked on the channel axis; vb [9,CO] = the taps applied to the

@@ -46,7 +46,9 @@ SIGNATURES = {
     "mvster_conv_narrow": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f],
     "mvster_conv_narrow4": [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f],
     "mvster_conv_narrow_pair": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f],
+    "mvster_conv_narrow_pair_planes": [_f] + [_i] * 4 + [_f] * 7 + [_i] * 3 + [_f, _i, _f, _f, _i, _f] + [_i] * 4 + [_f],
     "mvster_deconv_select": [_f] * 14 + [_i] * 6 + [_fl, _f],
+    "mvster_deconv_select_riders": [_f] * 14 + [_i] * 6 + [_fl] + [_f] * 4 + [_i] * 3 + [_f],
     "mvster_deconv_small": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f],
     "mvster_fpn_tail_gather": [_f, _f, _f, _f, _i, _i, _i, _i, _f],
     "mvster_fpn_lateral_up": [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f],

@@ -650,9 +650,14 @@ def _up3d(seq, prob=None):
     return ConvLayer(ct.weight, True, ct.stride, ct.padding, bn=bn, relu=True, prob=prob)
 
 
-def fused_conv11_select(L, t, c0, hypo, split_itv, inverse_depth, want_logits=False):
+RIDER_DEPTHS = (4, 8)           # the selection launches that take riders (deconv_select_mfma_kernel)
+
+
+def fused_conv11_select(L, t, c0, hypo, split_itv, inverse_depth, want_logits=False, upsample=None, up_size=None):
     """reg2d's conv11 (+ BatchNorm, ReLU, skip c0) + `prob` + softmax / argmax / gather / bounds in one launch
-    (mvster_deconv_select): t [B,D,hi,wi,16], c0 [B,D,2hi,2wi,8], hypo [B,D,2hi,2wi] -> the stage's selection dict."""
+    (mvster_deconv_select): t [B,D,hi,wi,16], c0 [B,D,2hi,2wi,8], hypo [B,D,2hi,2wi] -> the stage's selection dict.
+    ``upsample``: up to three finished [B,h,w] maps that the same launch interpolates to ``up_size`` = (H, W), the bits of
+    ``ops.upsample_bilinear_multi`` (entry "upsampled" of the dict, a list); D must be one of RIDER_DEPTHS then."""
     B, D, hi, wi, _ = t.shape
     dev = t.device
     hypo = hypo.contiguous()
@@ -662,13 +667,37 @@ def fused_conv11_select(L, t, c0, hypo, split_itv, inverse_depth, want_logits=Fa
     imin = torch.empty_like(depth) if inverse_depth else None
     imax = torch.empty_like(depth) if inverse_depth else None
     lo = torch.empty_like(attn) if want_logits else None
-    rc = _lib.load().mvster_deconv_select(
-        t.data_ptr(), L.w_deconv.data_ptr(), L.scale.data_ptr(), L.shift.data_ptr(), c0.data_ptr(),
-        L.prob[0].data_ptr(), L.prob[1].data_ptr(), hypo.data_ptr(), attn.data_ptr(), depth.data_ptr(), conf.data_ptr(),
-        None if imin is None else imin.data_ptr(), None if imax is None else imax.data_ptr(),
-        None if lo is None else lo.data_ptr(), B, D, hi, wi, L.cin, int(L.relu), float(split_itv), ops._stream())
+    args = (t.data_ptr(), L.w_deconv.data_ptr(), L.scale.data_ptr(), L.shift.data_ptr(), c0.data_ptr(),
+            L.prob[0].data_ptr(), L.prob[1].data_ptr(), hypo.data_ptr(), attn.data_ptr(), depth.data_ptr(), conf.data_ptr(),
+            None if imin is None else imin.data_ptr(), None if imax is None else imax.data_ptr(),
+            None if lo is None else lo.data_ptr(), B, D, hi, wi, L.cin, int(L.relu), float(split_itv))
+    ups = None
+    if upsample:
+        import ctypes
+        xs = [x.contiguous() for x in upsample]
+        H, W = up_size
+        n = len(xs)
+        for i, x in enumerate(xs):
+            if x.dim() != 3 or x.shape[0] != B or x.device != dev or x.dtype != torch.float32 or x.shape[1] < 1 or x.shape[2] < 1:
+                raise RuntimeError("fused_conv11_select: upsample[%d] is %s %s on %s, expected float32 [%d,h,w] on %s"
+                                   % (i, x.dtype, tuple(x.shape), x.device, B, dev))
+        if n > 3 or H < 1 or W < 1 or D not in RIDER_DEPTHS:
+            raise RuntimeError("fused_conv11_select: %d maps to %dx%d beside D = %d: at most 3 maps, D in %s"
+                               % (n, H, W, D, RIDER_DEPTHS))
+        ups = [torch.empty(B, H, W, device=dev, dtype=torch.float32) for _ in xs]
+        ip = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
+        op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in ups])
+        hs = (ctypes.c_int * n)(*[x.shape[1] for x in xs])
+        ws = (ctypes.c_int * n)(*[x.shape[2] for x in xs])
+        rc = _lib.load().mvster_deconv_select_riders(*args, ctypes.cast(ip, ctypes.c_void_p), ctypes.cast(op, ctypes.c_void_p),
+                                                     ctypes.cast(hs, ctypes.c_void_p), ctypes.cast(ws, ctypes.c_void_p), n, H, W,
+                                                     ops._stream())
+    else:
+        rc = _lib.load().mvster_deconv_select(*args, ops._stream())
     _lib.check(rc, "deconv_select")
     out = {"attn_weight": attn, "depth": depth, "conf": conf}
+    if ups is not None:
+        out["upsampled"] = ups
     if inverse_depth:
         out["inverse_min_depth"], out["inverse_max_depth"] = imin, imax
     if want_logits:
@@ -706,10 +735,12 @@ class Reg2dPlan:
         t = self.conv9(t, skip=c2, skip_mode=SKIP_ADD)
         return self.conv11(t, skip=c0, skip_mode=SKIP_ADD)
 
-    def select(self, x, hypo, split_itv, inverse_depth, want_logits=False):
+    def select(self, x, hypo, split_itv, inverse_depth, want_logits=False, upsample=None, up_size=None):
         """x [B,D,h,w,G] -> the stage's selection dict (ops.select_depth's): the U-Net, then conv11 + `prob` + softmax +
         argmax + gather + bounds in ONE launch (mvster_deconv_select) when conv11 runs on the narrow deconvolution kernel;
-        otherwise logits + ops.select_depth.  Same bits either way."""
+        otherwise logits + ops.select_depth.  Same bits either way.  ``upsample`` / ``up_size``: finished maps for the fused
+        launch to interpolate (``fused_conv11_select``); where that launch is not taken or takes no riders the dict has no
+        "upsampled" entry and the caller interpolates them itself."""
         c0 = self.conv0(x)
         c2 = self.conv2(self.conv1(c0))
         c4 = self.conv4(self.conv3(c2))
@@ -720,6 +751,9 @@ class Reg2dPlan:
         B, D, hi, wi, _ = t.shape
         if (FUSE_SELECT and L.w_deconv is not None and L.prob is not None and L.cin == 16 and FORCE_VARIANT in (None, 4)
                 and 2 <= D <= 16 and t.is_contiguous() and c0.is_contiguous()):
+            if upsample and D in RIDER_DEPTHS and len(upsample) <= 3:
+                # (keywords: callers' wrappers of this function pass everything behind `hypo` through)
+                return fused_conv11_select(L, t, c0, hypo, split_itv, inverse_depth, want_logits, upsample=upsample, up_size=up_size)
             return fused_conv11_select(L, t, c0, hypo, split_itv, inverse_depth, want_logits)
         res = self.conv11(t, skip=c0, skip_mode=SKIP_ADD)
         if self.fused_prob:
@@ -828,9 +862,11 @@ class FpnPlan:
             x = l(x)
         return x
 
-    def trunk(self, x):
-        """Bottom-up path + the first top-down map f1: what both branches below need."""
-        c0 = self._conv0(x)
+    def trunk(self, x, c0=None):
+        """Bottom-up path + the first top-down map f1: what both branches below need.  ``c0``: conv0's output where the caller
+        already has it (``conv0_planes``); ``x`` is not read then."""
+        if c0 is None:
+            c0 = self._conv0(x)
         c1 = self._seq(self.conv1, c0)
         c2 = self._seq(self.conv2, c1)
         c3 = self._seq(self.conv3, c2)
@@ -852,6 +888,59 @@ class FpnPlan:
             _lib.check(rc, "conv_narrow_pair")
             return out
         return self._seq(self.conv0, x)
+
+    def conv0_planes(self, imgs, side=None):
+        """``_conv0`` of ``ops.pack_images(imgs)`` without the RGB0 copy: conv_narrow_pair_kernel's planar form reads the views'
+        [B,3,H,W] planes itself (mvster_conv_narrow_pair_planes; 72 instead of 124 MB of HBM traffic for pack + conv0 at
+        5 x 512 x 640).  ``side`` = (proj_list, depth_values, D, h, w, inverse), the arguments of ``ops.forward_prologue`` behind
+        the images: its two small jobs ride in the launch.  -> (c0 [N*B,1,H,W,8], rt, hypo) with rt = hypo = None without
+        ``side``; None where ``_conv0`` would not take the pair kernel or the images are not N <= 8 contiguous fp32 [B,3,H,W]
+        tensors on the weights' device (the caller packs and calls ``trunk`` as before).  Same bits either way."""
+        import ctypes
+        a, b = self.conv0
+        x0 = imgs[0]
+        if not (FUSE_CONV0 and FORCE_VARIANT is None and a.w_small is not None and b.w_small is not None and a.cin == 4 and b.cin == 8
+                and 1 <= len(imgs) <= 8 and x0.dim() == 4 and x0.shape[1] == 3 and x0.is_cuda and a.w_small.device == x0.device
+                and hasattr(_lib.load(), "mvster_conv_narrow_pair_planes")):
+            return None
+        B, _, H, W = x0.shape
+        N = len(imgs)
+        if N * B * H * W < NARROW_PAIR_MIN_PIXELS:
+            return None
+        for im in imgs:
+            if im.shape != x0.shape or im.device != x0.device or im.dtype != torch.float32 or not im.is_contiguous():
+                return None
+        dev = x0.device
+        out = torch.empty((N * B, 1, H, W, 8), device=dev, dtype=torch.float32)
+        ip = (ctypes.c_void_p * N)(*[im.data_ptr() for im in imgs])
+        rt = hypo = pp = None
+        nstage = ndv = D = h = w = inverse = 0
+        if side is not None:
+            # (raw pointers go to the kernel: every shape it derives addresses from is checked here, as in ops.forward_prologue)
+            proj_list, dv, D, h, w, inverse = side
+            pms = [p.contiguous() for p in proj_list]
+            dv = dv.contiguous()
+            for k, pm in enumerate(pms):
+                if tuple(pm.shape) != (B, N, 2, 4, 4) or pm.device != dev or pm.dtype != torch.float32:
+                    raise RuntimeError("conv0_planes: proj_list[%d] is %s %s, expected float32 [%d,%d,2,4,4]"
+                                       % (k, pm.dtype, tuple(pm.shape), B, N))
+            if dv.dim() != 2 or dv.shape[0] != B or dv.shape[1] < 2 or dv.device != dev or dv.dtype != torch.float32:
+                raise RuntimeError("conv0_planes: depth_values is %s %s, expected float32 [%d, >= 2]" % (dv.dtype, tuple(dv.shape), B))
+            if N < 2 or not 1 <= len(pms) <= 8 or D < 2 or h < 1 or w < 1:
+                raise RuntimeError("conv0_planes: bad side jobs (%d views, %d stages, hypothesis volume %dx%dx%d)"
+                                   % (N, len(pms), D, h, w))
+            nstage, ndv = len(pms), dv.shape[1]
+            rt = torch.empty(nstage, B, N - 1, 12, device=dev, dtype=torch.float32)
+            hypo = torch.empty(B, D, h, w, device=dev, dtype=torch.float32)
+            pp = (ctypes.c_void_p * nstage)(*[p.data_ptr() for p in pms])
+        rc = _lib.load().mvster_conv_narrow_pair_planes(
+            ctypes.cast(ip, ctypes.c_void_p), N, B, H, W, a.w_small.data_ptr(), a.scale.data_ptr(), a.shift.data_ptr(),
+            b.w_small.data_ptr(), b.scale.data_ptr(), b.shift.data_ptr(), out.data_ptr(), int(a.relu), int(b.relu), NARROW_PAIR_WPC,
+            None if pp is None else ctypes.cast(pp, ctypes.c_void_p), nstage, None if rt is None else rt.data_ptr(),
+            None if side is None else dv.data_ptr(), ndv, None if hypo is None else hypo.data_ptr(), D, h, w, int(bool(inverse)),
+            ops._stream())
+        _lib.check(rc, "conv_narrow_pair_planes")
+        return out, rt, hypo
 
     def coarse(self, c3, f1):
         """Output convs of the two coarse levels: everything stages 1 and 2 need."""

@@ -131,9 +131,19 @@ int dispatch_1x1(const ConvArgs& a, int mt, int wpc, hipStream_t s);
 
 // deconv_select.hip: reg2d's last layer + `prob` + the depth selection on MFMA tiles, persistent LDS-DMA ring (D in {4, 8};
 // MVSTER_ERR_UNSUPPORTED otherwise: the VALU kernel of conv_small.hip runs)
+// `up` (optional): up to three [B, hi, wi] maps interpolated to [B, ho, wo] (bilinear, align_corners) by workgroups behind the
+// selection's own, UP_PPT pixels per thread -- the coarse stages' confidence maps at the last stage (mvster_deconv_select_riders)
+constexpr int UP_PPT = 4;
+struct UpRiders {
+    const float* in[3] = {nullptr, nullptr, nullptr};
+    float* out[3] = {nullptr, nullptr, nullptr};
+    int hi[3] = {0, 0, 0}, wi[3] = {0, 0, 0};
+    int n = 0, ho = 0, wo = 0;
+    unsigned per_map = 1, nwg = 0;      // workgroups per map / in all (filled by the launcher)
+};
 int dispatch_deconv_select_mfma(const float* in, const float* w, const float* scale, const float* shift, const float* skip,
                                 const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth,
                                 float* conf, float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi, int Wi,
-                                int relu, float split_itv, hipStream_t s);
+                                int relu, float split_itv, const UpRiders* up, hipStream_t s);
 
 }  // namespace mvconv

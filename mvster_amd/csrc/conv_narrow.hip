@@ -20,6 +20,8 @@
 // K order = (ky, kx', ci) with ci in the fragment permutation; products with the structural zeros are exact no-ops for
 // finite inputs (a non-finite input pixel reaches one more output column than in the reference: 0 * inf).
 // Reference layers: models/mvs4net_utils.py:427-428 (FPN conv0), :875 (reg2d conv0), :459 (out4, composed, section 4.3).
+#include <type_traits>
+
 #include "conv_args.hpp"
 
 namespace {
@@ -301,6 +303,45 @@ struct NarrowPairArgs {
     FastDiv tiles_x, tiles_y;
 };
 
+// The planar form: the loading waves read the views' own [B, 3, H, W] planes, so that the RGB0 copy is neither
+// written nor read back (26 + 26 MB at 5 x 512 x 640 become 20 MB read once), and the two small jobs every forward starts
+// with -- the stages' relative projections and the first stage's hypotheses (forward_prologue_kernel's) -- run in `nside`
+// extra workgroups with the lowest block indices (dispatched first: the serial fp64 inverses take ~7 us).
+struct NarrowPlanesArgs : NarrowPairArgs {
+    const float* img[8];  // N views, each [B, 3, H, W]; batch index of the tiles nb = v * B + b
+    FastDiv bdiv;         // by B
+    unsigned img_bytes;   // B * 3 * H * W * 4
+    unsigned nside, nproj;   // side workgroups in all / of the projections (the first ones)
+    const float* pm[8];   // per stage [B, N, 2, 4, 4]
+    float* rt;            // [nstage, B, N - 1, 12]
+    const float* dv;      // [B, ndv]
+    float* hypo;          // [B, D, hw]
+    int nstage, N, B, ndv, D, hw, inverse;
+};
+
+// Same device functions as forward_prologue_kernel (stage_ops.hip): the same bits.
+__device__ __forceinline__ void pair_side_jobs(const NarrowPlanesArgs& a, unsigned sb) {
+    if (sb < a.nproj) {
+        const int p = (int)(sb * 512 + threadIdx.x);
+        const int NV = a.N - 1;
+        const int per = a.B * NV;
+        if (p >= a.nstage * per) return;
+        const int s = p / per, r = p - s * per;
+        const int b = r / NV, v = r - b * NV;
+        mv::RT m;
+        mv::relative_projection(a.pm[s] + ((long)b * a.N) * 32, a.pm[s] + ((long)b * a.N + v + 1) * 32, m);
+        float* o = a.rt + (long)p * 12;
+        for (int k = 0; k < 9; ++k) o[k] = m.r[k];
+        for (int k = 0; k < 3; ++k) o[9 + k] = m.t[k];
+    } else {
+        const int p = (int)((sb - a.nproj) * 512 + threadIdx.x);
+        if (p >= a.hw) return;
+        for (int b = 0; b < a.B; ++b)
+            mv::init_range_pixel(a.dv[b * a.ndv], a.dv[b * a.ndv + a.ndv - 1], a.hypo + (long)b * a.D * a.hw, a.D, a.hw, p,
+                                 a.inverse);
+    }
+}
+
 struct PairGeom {
     static constexpr int TY = 14, TX = 64;
     static constexpr int MH = TY + 2, MW = TX + 2;             // mid tile (first layer's outputs)
@@ -313,8 +354,8 @@ struct PairGeom {
     static constexpr size_t LDS = (size_t)(R * STAGE + MID + 8) * 16;   // + scale / shift of both layers
 };
 
-template <int DBG>
-__global__ void __launch_bounds__(512, 4) conv_narrow_pair_kernel(NarrowPairArgs a) {
+template <int DBG, bool PLANES = false>
+__global__ void __launch_bounds__(512, 4) conv_narrow_pair_kernel(std::conditional_t<PLANES, NarrowPlanesArgs, NarrowPairArgs> a) {
     using G = PairGeom;
     constexpr int TY = G::TY, PW = G::PW, MW = G::MW, NIW = G::NIW;
     static_assert(G::MH == 16, "the extra pixel pairs of the mid tile's rows form exactly one 16-row MFMA unit");
@@ -327,8 +368,16 @@ __global__ void __launch_bounds__(512, 4) conv_narrow_pair_kernel(NarrowPairArgs
     const int wave = wave8 & 3;
     const bool loader = wave8 >= 4;
     const int lm = lane & 15, lq = lane >> 4;
-    const unsigned nwg = gridDim.x;
-    unsigned tile = xcd_remap(blockIdx.x, nwg);
+    unsigned nwg = gridDim.x, bid = blockIdx.x;
+    if constexpr (PLANES) {
+        if (bid < a.nside) {                                    // (workgroup-uniform)
+            pair_side_jobs(a, bid);
+            return;
+        }
+        bid -= a.nside;
+        nwg -= a.nside;
+    }
+    unsigned tile = xcd_remap(bid, nwg);
     if (PAIR_DBG & 16) tile = a.ntiles;
 
     auto decode = [&](unsigned t, int& nb, int& y0, int& x0) {
@@ -338,7 +387,69 @@ __global__ void __launch_bounds__(512, 4) conv_narrow_pair_kernel(NarrowPairArgs
         x0 = (int)txu * G::TX;
     };
 
-    if (loader) {
+    if constexpr (PLANES) {
+        if (loader) {
+            // Each patch pixel's three plane values by 4-byte buffer loads (lanes walk a patch row: coalesced), {r, g, b, 0}
+            // assembled in registers and written to the slot the DMA form fills.  The registers are the third ring stage: tile
+            // i + 2 is fetched while tile i computes and moves to LDS one tile later, after barrier (1) of tile i + 1 (into stage
+            // i & 1, which phase 1 of tile i read last, before its barrier (2)): the loads have a whole tile's time to land.
+            int dpos[NIW];                                      // column | row << 8; -1 = a surplus slot
+            unsigned dpix[NIW];                                 // byte offset of the slot in its plane, from the patch origin
+#pragma unroll
+            for (int n = 0; n < NIW; ++n) {
+                const int s = (wave + 4 * n) * 64 + lane;
+                const int prow = s / PW, pl = s - prow * PW;
+                dpos[n] = s < G::PSLOTS ? (pl | (prow << 8)) : -1;
+                dpix[n] = (unsigned)((prow * a.W + pl) * 4);
+            }
+            const unsigned plane = (unsigned)(a.H * a.W * 4);
+            unsigned px[NIW][3];
+            auto load_tile = [&](unsigned t) {
+                int nb, y0, x0;
+                decode(t, nb, y0, x0);
+                unsigned bu;
+                const unsigned v = __builtin_amdgcn_readfirstlane(fdivmod((unsigned)nb, a.bdiv, bu));
+                const __amdgpu_buffer_rsrc_t rsrc =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.img[v]), (short)0, (int)a.img_bytes, 0x00020000);
+                const unsigned porigin = (unsigned)(((((int)bu * 3 * a.H + y0 - 2) * a.W) + x0 - 2) * 4);   // (32-bit wrap-around on borders)
+#pragma unroll
+                for (int n = 0; n < NIW; ++n) {
+                    const int ix = x0 + (dpos[n] & 255) - 2, iy = y0 + (dpos[n] >> 8) - 2;
+                    const bool ok = dpos[n] >= 0 && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W && !(PAIR_DBG & 8);
+                    // (out of the image: past the descriptor's range, which reads as zero -- the plane offsets below stay under 2^31)
+                    const unsigned off = ok ? dpix[n] + porigin : 0x80000000u;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const int offc = (int)(off + (unsigned)c * plane);      // (a named operand, as for the DMA builtin)
+                        px[n][c] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, offc, 0, 0);
+                    }
+                }
+            };
+            auto write_tile = [&](int stage) {
+                f32x4v* const dst0 = lds + stage * G::STAGE;
+#pragma unroll
+                for (int n = 0; n < NIW; ++n)
+                    dst0[(wave + 4 * n) * 64 + lane] = (f32x4v){__builtin_bit_cast(float, px[n][0]), __builtin_bit_cast(float, px[n][1]),
+                                                                __builtin_bit_cast(float, px[n][2]), 0.0f};
+            };
+            if (tile < a.ntiles) {
+                load_tile(tile);
+                write_tile(0);
+            }
+            if (tile + nwg < a.ntiles) load_tile(tile + nwg);
+            __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): the first patch is in LDS
+            int st = 1;
+            for (; tile < a.ntiles; tile += nwg) {
+                __builtin_amdgcn_s_barrier();                   // (1) patch of this tile visible
+                if (tile + nwg < a.ntiles) write_tile(st);      // the next tile's patch: its stage was read last a tile ago
+                st ^= 1;
+                if (tile + 2u * nwg < a.ntiles) load_tile(tile + 2u * nwg);
+                __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): LDS writes count there, not in vmcnt
+                __builtin_amdgcn_s_barrier();                   // (2)
+            }
+            return;
+        }
+    } else if (loader) {
         const __amdgpu_buffer_rsrc_t in_rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), (short)0, (int)a.in_bytes, 0x00020000);
         unsigned dbase[NIW];
@@ -599,6 +710,28 @@ __global__ void __launch_bounds__(512, 4) conv_narrow_pair_kernel(NarrowPairArgs
     }
 }
 
+// tile counts of a launch and its grid: equal shares of the tiles for at most `wpc` (default 2) workgroups per CU
+int pair_grid(NarrowPairArgs& a, int wpc, long& gx) {
+    using G = PairGeom;
+    const int ncu = mvconv::num_cus();
+    if (ncu <= 0) return MVSTER_ERR_LAUNCH;
+    const unsigned tx = (unsigned)((a.W + G::TX - 1) / G::TX), ty = (unsigned)((a.H + G::TY - 1) / G::TY);
+    const long ntiles = (long)tx * ty * a.NB;
+    if (ntiles >= (1L << 30)) return MVSTER_ERR_SHAPE;
+    a.ntiles = (unsigned)ntiles;
+    a.tiles_x = mv_fastdiv(tx);
+    a.tiles_y = mv_fastdiv(ty);
+    const int by_lds = (int)((160 * 1024) / G::LDS);
+    int per_cu = wpc > 0 ? wpc : 2;
+    if (per_cu > by_lds) per_cu = by_lds;
+    if (per_cu > 2) per_cu = 2;
+    if (per_cu < 1) per_cu = 1;
+    const long gmax = (long)ncu * per_cu;
+    const long rounds = (ntiles + gmax - 1) / gmax;            // equal shares
+    gx = (ntiles + rounds - 1) / rounds;
+    return MVSTER_OK;
+}
+
 int launch_narrow_pair(NarrowPairArgs& a, int wpc, hipStream_t s) {
     using G = PairGeom;
     auto kern = conv_narrow_pair_kernel<0>;
@@ -616,24 +749,23 @@ int launch_narrow_pair(NarrowPairArgs& a, int wpc, hipStream_t s) {
     static unsigned long attr_done_all[13] = {0};
     unsigned long& attr_done = attr_done_all[slot];
     if (G::LDS > 64 * 1024 && !mvconv::allow_big_lds(reinterpret_cast<const void*>(kern), attr_done)) return MVSTER_ERR_LAUNCH;
-    const int ncu = mvconv::num_cus();
-    if (ncu <= 0) return MVSTER_ERR_LAUNCH;
-    const unsigned tx = (unsigned)((a.W + G::TX - 1) / G::TX), ty = (unsigned)((a.H + G::TY - 1) / G::TY);
-    const long ntiles = (long)tx * ty * a.NB;
-    if (ntiles >= (1L << 30)) return MVSTER_ERR_SHAPE;
-    a.ntiles = (unsigned)ntiles;
-    a.tiles_x = mv_fastdiv(tx);
-    a.tiles_y = mv_fastdiv(ty);
-    const int by_lds = (int)((160 * 1024) / G::LDS);
-    int per_cu = wpc > 0 ? wpc : 2;
-    if (per_cu > by_lds) per_cu = by_lds;
-    if (per_cu > 2) per_cu = 2;
-    if (per_cu < 1) per_cu = 1;
-    const long gmax = (long)ncu * per_cu;
-    const long rounds = (ntiles + gmax - 1) / gmax;            // equal shares
-    const long gx = (ntiles + rounds - 1) / rounds;
+    long gx;
+    if (const int rc = pair_grid(a, wpc, gx)) return rc;
     MV_NOTE_KERNEL("conv_narrow_pair_kernel");
     hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), G::LDS, s, a);
+    return mv_check_launch();
+}
+
+// The planar form: the same grid of tile workgroups behind a.nside side workgroups.
+int launch_narrow_pair_planes(NarrowPlanesArgs& a, int wpc, hipStream_t s) {
+    using G = PairGeom;
+    auto kern = conv_narrow_pair_kernel<0, true>;
+    static unsigned long attr_done = 0;
+    if (G::LDS > 64 * 1024 && !mvconv::allow_big_lds(reinterpret_cast<const void*>(kern), attr_done)) return MVSTER_ERR_LAUNCH;
+    long gx;
+    if (const int rc = pair_grid(a, wpc, gx)) return rc;
+    MV_NOTE_KERNEL("conv_narrow_pair_kernel<0, true>");
+    hipLaunchKernelGGL(kern, dim3((unsigned)(gx + a.nside)), dim3(512), G::LDS, s, a);
     return mv_check_launch();
 }
 
@@ -702,4 +834,48 @@ extern "C" int mvster_conv_narrow_pair(const float* in, const float* w1, const f
     a.in_bytes = (unsigned)in_bytes; a.out_bytes = (unsigned)out_bytes;
     a.dbg = wpc >> 4;                                           // (read by the probe build only)
     return launch_narrow_pair(a, wpc & 15, (hipStream_t)stream);
+}
+
+// mvster_pack_images + mvster_conv_narrow_pair in one launch, without the RGB0 copy: imgs = N <= 8 views, each a contiguous
+// [B,3,H,W] block (any 4-byte alignment); out [N*B,H,W,8], batch index v * B + b; the same bits.  With proj_matrices non-null
+// the launch also does what mvster_forward_prologue does beside its pack (same arguments, same bits): rt [nstage,B,N-1,12]
+// and hypo [B,D,h,w], in a few extra workgroups dispatched ahead of the tiles.
+extern "C" int mvster_conv_narrow_pair_planes(const float* const* imgs, int N, int B, int H, int W, const float* w1,
+                                              const float* scale1, const float* shift1, const float* w2, const float* scale2,
+                                              const float* shift2, float* out, int relu1, int relu2, int wpc,
+                                              const float* const* proj_matrices, int nstage, float* rt,
+                                              const float* depth_values, int ndv, float* hypo, int D, int h, int w, int inverse,
+                                              void* stream) {
+    if (!imgs || !w1 || !scale1 || !shift1 || !w2 || !scale2 || !shift2 || !out) return MVSTER_ERR_NULL;
+    if (N < 1 || N > 8 || B <= 0 || H <= 0 || W <= 0) return MVSTER_ERR_SHAPE;
+    const long img_bytes = (long)B * 3 * H * W * 4, out_bytes = (long)N * B * H * W * 32;
+    if (img_bytes >= (1L << 31) || out_bytes >= (1L << 31)) return MVSTER_ERR_SHAPE;
+    NarrowPlanesArgs a;
+    for (int v = 0; v < 8; ++v) {
+        if (v < N && !imgs[v]) return MVSTER_ERR_NULL;
+        if (v < N && ((uintptr_t)imgs[v] & 3)) return MVSTER_ERR_SHAPE;
+        a.img[v] = imgs[v < N ? v : 0];
+    }
+    a.in = nullptr; a.w1 = w1; a.scale1 = scale1; a.shift1 = shift1; a.w2 = w2; a.scale2 = scale2; a.shift2 = shift2; a.out = out;
+    a.NB = N * B; a.H = H; a.W = W; a.relu1 = relu1; a.relu2 = relu2; a.dbg = 0;
+    a.in_bytes = 0; a.out_bytes = (unsigned)out_bytes;
+    a.bdiv = mv_fastdiv((unsigned)B); a.img_bytes = (unsigned)img_bytes;
+    a.nside = a.nproj = 0;
+    for (int s = 0; s < 8; ++s) a.pm[s] = nullptr;
+    a.rt = nullptr; a.dv = nullptr; a.hypo = nullptr;
+    a.nstage = 0; a.N = N; a.B = B; a.ndv = 0; a.D = 0; a.hw = 0; a.inverse = 0;
+    if (proj_matrices) {
+        if (!rt || !depth_values || !hypo) return MVSTER_ERR_NULL;
+        if (N < 2 || nstage < 1 || nstage > 8 || D < 2 || h <= 0 || w <= 0 || ndv < 1 || (long)h * w >= (1L << 30))
+            return MVSTER_ERR_SHAPE;
+        for (int s = 0; s < nstage; ++s) {
+            if (!proj_matrices[s]) return MVSTER_ERR_NULL;
+            a.pm[s] = proj_matrices[s];
+        }
+        a.rt = rt; a.dv = depth_values; a.hypo = hypo;
+        a.nstage = nstage; a.ndv = ndv; a.D = D; a.hw = h * w; a.inverse = inverse;
+        a.nproj = (unsigned)(((long)nstage * B * (N - 1) + 511) / 512);
+        a.nside = a.nproj + (unsigned)((a.hw + 511) / 512);
+    }
+    return launch_narrow_pair_planes(a, wpc & 15, (hipStream_t)stream);
 }

@@ -345,10 +345,10 @@ extern "C" int mvster_deconv_small(const float* in, const float* w, const float*
 // mvster_deconv_small (16 -> 8, fused `prob` head) + mvster_select_depth in one launch: in [B*D,Hi,Wi,16] (slices b*D + d),
 // skip [B*D,2Hi,2Wi,8] or null, hypo [B,D,2Hi,2Wi] -> attn [B,D,2Hi,2Wi], depth / conf / inv_min / inv_max [B,2Hi,2Wi]
 // (conf, inv_* optional), logits_out [B,D,2Hi,2Wi] optional.  Bit-identical to the two launches.  D <= 16.
-extern "C" int mvster_deconv_select(const float* in, const float* w, const float* scale, const float* shift, const float* skip,
-                                    const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth,
-                                    float* conf, float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi,
-                                    int Wi, int cin, int relu, float split_itv, void* stream) {
+static int deconv_select_impl(const float* in, const float* w, const float* scale, const float* shift, const float* skip,
+                              const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth,
+                              float* conf, float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi, int Wi,
+                              int cin, int relu, float split_itv, const mvconv::UpRiders* up, void* stream) {
     if (!in || !w || !scale || !shift || !prob_w || !prob_b || !hypo || !attn || !depth) return MVSTER_ERR_NULL;
     if ((inv_min == nullptr) != (inv_max == nullptr)) return MVSTER_ERR_NULL;
     if (B <= 0 || D < 2 || D > mv::kSelMaxD || Hi <= 0 || Wi <= 0 || (inv_min && D < 3)) return MVSTER_ERR_SHAPE;
@@ -358,8 +358,8 @@ extern "C" int mvster_deconv_select(const float* in, const float* w, const float
     {
         // D in {4, 8} (the shipped cascade): MFMA tiles on the persistent LDS-DMA ring, same bits (deconv_select.hip)
         const int rc = mvconv::dispatch_deconv_select_mfma(in, w, scale, shift, skip, prob_w, prob_b, hypo, attn, depth, conf, inv_min,
-                                                           inv_max, logits_out, B, D, Hi, Wi, relu, split_itv, (hipStream_t)stream);
-        if (rc != MVSTER_ERR_UNSUPPORTED) return rc;
+                                                           inv_max, logits_out, B, D, Hi, Wi, relu, split_itv, up, (hipStream_t)stream);
+        if (rc != MVSTER_ERR_UNSUPPORTED || up) return rc;         // (the riders exist on the MFMA kernel only)
     }
     DeconvArgs a;
     a.in = in; a.w = w; a.scale = scale; a.shift = shift; a.skip = skip; a.prob_w = prob_w; a.prob_b = prob_b;
@@ -370,4 +370,34 @@ extern "C" int mvster_deconv_select(const float* in, const float* w, const float
     MV_NOTE_KERNEL("deconv_select_kernel<16>");
     hipLaunchKernelGGL(deconv_select_kernel<16>, dim3((Hi * Wi + 63) / 64, B), dim3(64, D), 0, (hipStream_t)stream, a, so);
     return mv_check_launch();
+}
+
+extern "C" int mvster_deconv_select(const float* in, const float* w, const float* scale, const float* shift, const float* skip,
+                                    const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth,
+                                    float* conf, float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi,
+                                    int Wi, int cin, int relu, float split_itv, void* stream) {
+    return deconv_select_impl(in, w, scale, shift, skip, prob_w, prob_b, hypo, attn, depth, conf, inv_min, inv_max, logits_out, B, D,
+                              Hi, Wi, cin, relu, split_itv, nullptr, stream);
+}
+
+// mvster_deconv_select + mvster_upsample_bilinear_multi in one launch: up_ins[k] [B,up_his[k],up_wis[k]] -> up_outs[k]
+// [B,ho,wo], k < n <= 3, maps that are complete before the launch (the coarse stages' confidences at the last stage).  Same
+// bits as the two launches.  D in {4, 8} only (MVSTER_ERR_UNSUPPORTED otherwise: nothing was launched).
+extern "C" int mvster_deconv_select_riders(const float* in, const float* w, const float* scale, const float* shift,
+                                           const float* skip, const float* prob_w, const float* prob_b, const float* hypo,
+                                           float* attn, float* depth, float* conf, float* inv_min, float* inv_max,
+                                           float* logits_out, int B, int D, int Hi, int Wi, int cin, int relu, float split_itv,
+                                           const float* const* up_ins, float* const* up_outs, const int* up_his,
+                                           const int* up_wis, int n, int ho, int wo, void* stream) {
+    if (!up_ins || !up_outs || !up_his || !up_wis) return MVSTER_ERR_NULL;
+    if (n < 1 || n > 3 || ho <= 0 || wo <= 0 || B <= 0 || (long)B * ho * wo >= (1L << 31)) return MVSTER_ERR_SHAPE;
+    mvconv::UpRiders up;
+    for (int k = 0; k < n; ++k) {
+        if (!up_ins[k] || !up_outs[k]) return MVSTER_ERR_NULL;
+        if (up_his[k] <= 0 || up_wis[k] <= 0) return MVSTER_ERR_SHAPE;
+        up.in[k] = up_ins[k]; up.out[k] = up_outs[k]; up.hi[k] = up_his[k]; up.wi[k] = up_wis[k];
+    }
+    up.n = n; up.ho = ho; up.wo = wo;
+    return deconv_select_impl(in, w, scale, shift, skip, prob_w, prob_b, hypo, attn, depth, conf, inv_min, inv_max, logits_out, B, D,
+                              Hi, Wi, cin, relu, split_itv, &up, stream);
 }

@@ -34,6 +34,7 @@ struct DselArgs {
     float split_itv;
     unsigned in_bytes, skip_bytes, ntiles;
     FastDiv tiles_x, tiles_y;
+    mvconv::UpRiders up;      // up.nwg workgroups behind the selection's own run them
 };
 
 template <int D, int RI, int R>
@@ -66,7 +67,21 @@ __global__ void __launch_bounds__(512) deconv_select_mfma_kernel(DselArgs a) {
     const bool loader = wave8 >= 4;
     const int lm = lane & 15, lq = lane >> 4;
     const int Ho = 2 * a.Hi, Wo = 2 * a.Wi;
-    const unsigned nwg = gridDim.x;
+    const unsigned nwg = gridDim.x - a.up.nwg;
+    if (blockIdx.x >= nwg) {                                    // (workgroup-uniform; no table: never taken)
+        // riders: maps that were complete before this launch, interpolated to the output size (the coarse stages' confidences;
+        // upsample_bilinear_multi_kernel's per-pixel body), UP_PPT pixels per thread
+        const int npix = a.up.ho * a.up.wo;
+        const unsigned r = blockIdx.x - nwg, k = r / a.up.per_map, c = r - k * a.up.per_map;
+#pragma unroll
+        for (int i = 0; i < mvconv::UP_PPT; ++i) {
+            const long q = ((long)c * mvconv::UP_PPT + i) * 512 + threadIdx.x;
+            if (q >= (long)a.B * npix) break;
+            const int b = (int)(q / npix), p = (int)(q - (long)b * npix);
+            a.up.out[k][q] = mv::upsample_pixel(a.up.in[k] + (long)b * a.up.hi[k] * a.up.wi[k], a.up.hi[k], a.up.wi[k], a.up.ho, a.up.wo, p);
+        }
+        return;
+    }
     unsigned tile = xcd_remap(blockIdx.x, nwg);
 
     auto decode = [&](unsigned t, int& b, int& i0, int& j0) {
@@ -266,8 +281,12 @@ int launch_dsel(DselArgs& a, hipStream_t s) {
     const long gmax = (long)ncu * per_cu;
     const long rounds = (ntiles + gmax - 1) / gmax;
     const long gx = (ntiles + rounds - 1) / rounds;
+    if (a.up.n > 0) {
+        a.up.per_map = (unsigned)(((long)a.B * a.up.ho * a.up.wo + 512 * mvconv::UP_PPT - 1) / (512 * mvconv::UP_PPT));
+        a.up.nwg = a.up.per_map * (unsigned)a.up.n;
+    }
     MV_NOTE_KERNEL("deconv_select_mfma_kernel<%d, %d, %d>", D, RI, R);
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), G::LDS, s, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)gx + a.up.nwg), dim3(512), G::LDS, s, a);
     return mv_check_launch();
 }
 
@@ -279,7 +298,7 @@ namespace mvconv {
 int dispatch_deconv_select_mfma(const float* in, const float* w, const float* scale, const float* shift, const float* skip,
                                 const float* prob_w, const float* prob_b, const float* hypo, float* attn, float* depth,
                                 float* conf, float* inv_min, float* inv_max, float* logits_out, int B, int D, int Hi, int Wi,
-                                int relu, float split_itv, hipStream_t s) {
+                                int relu, float split_itv, const UpRiders* up, hipStream_t s) {
     const long in_bytes = (long)B * D * Hi * Wi * 64, skip_bytes = (long)B * D * Hi * Wi * 4 * 32;
     if (in_bytes >= (1L << 31) || skip_bytes >= (1L << 31)) return MVSTER_ERR_UNSUPPORTED;
     DselArgs a;
@@ -287,6 +306,9 @@ int dispatch_deconv_select_mfma(const float* in, const float* w, const float* sc
     a.attn = attn; a.depth = depth; a.conf = conf; a.inv_min = inv_min; a.inv_max = inv_max; a.logits_out = logits_out;
     a.B = B; a.Hi = Hi; a.Wi = Wi; a.relu = relu; a.split_itv = split_itv;
     a.in_bytes = (unsigned)in_bytes; a.skip_bytes = (unsigned)skip_bytes;
+    a.up = UpRiders();
+    if (up) a.up = *up;
+    a.up.nwg = 0;
     const int ncu = num_cus();
     if (D == 4) {
         // two-row tiles.  Large maps: two ring stages = 63 KB of LDS = two workgroups per CU (25.3 us at stage 4, 119 us at

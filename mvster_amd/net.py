@@ -321,15 +321,20 @@ class MVS4net(nn.Module):
             depth_interval = (depth_values[:, -1] - depth_values[:, 0]) / depth_values.size(1)
         names = ["stage%d" % (s + 1) for s in range(self.num_stage)]
         pms = [proj_matrices[n].to(dev, torch.float32) for n in names]
-        hypo0 = None
+        hypo0 = packed = c0 = None
         if self.merge_launches and (teacher is None or "stage1" not in teacher) and not self.fuse_hypotheses:
-            # pack + projections + the first stage's hypotheses: one launch instead of three
-            # (stage 1 reads the coarsest FPN level: H/8 x W/8)
-            packed, rts, hypo0 = ops.forward_prologue(imgs, pms, depth_values, self.stage_splits[0], H // 8, W // 8,
-                                                      self.inverse_depth)
+            # projections + the first stage's hypotheses (stage 1 reads the coarsest FPN level: H/8 x W/8) in the launch of
+            # FPN conv0, which reads the image planes itself; where conv0 does not run on that kernel (small maps, forced
+            # variants, FUSE_CONV0 off): with the pack, one launch instead of three
+            jobs = (pms, depth_values, self.stage_splits[0], H // 8, W // 8, self.inverse_depth)
+            fused = fpn.conv0_planes(imgs, jobs)
+            if fused is not None:
+                c0, rts, hypo0 = fused
+            else:
+                packed, rts, hypo0 = ops.forward_prologue(imgs, *jobs)
         else:
             packed, rts = ops.pack_images(imgs), ops.relative_projection_multi(pms)
-        c0, c1, c3, f1 = fpn.trunk(packed)                                       # channels-last [N*B,1,h,w,C]
+        c0, c1, c3, f1 = fpn.trunk(packed, c0=c0)                                # channels-last [N*B,1,h,w,C]
         main = torch.cuda.current_stream()
         side = None
         if self.overlap_streams and self.num_stage > 2:
@@ -368,6 +373,7 @@ class MVS4net(nn.Module):
         launch (``fuse_hypotheses``: that entry has no counted form)."""
         outputs = {}
         prev = None
+        ups = None                                                               # the coarse confidences at full resolution
         for s in range(self.num_stage):
             name = "stage%d" % (s + 1)
             if s == 2 and join is not None:
@@ -407,8 +413,14 @@ class MVS4net(nn.Module):
             plan = regs[s]
             want_logits = capture is not None
             if isinstance(plan, Reg2dPlan):
-                # (the U-Net's last layer, the prob head and the selection in one launch where the plan allows it)
-                sel = plan.select(cor, hypo, self.depth_interals_ratio[s], self.inverse_depth, want_logits=want_logits)
+                # (the U-Net's last layer, the prob head and the selection in one launch where the plan allows it; with
+                #  `merge_launches` the last stage's also interpolates the coarse stages' confidence maps, complete by then)
+                riders = None
+                if self.merge_launches and s == 3 and s == self.num_stage - 1:
+                    riders = [outputs["stage%d" % (k + 1)]["photometric_confidence"] for k in range(3)]
+                sel = plan.select(cor, hypo, self.depth_interals_ratio[s], self.inverse_depth, want_logits=want_logits,
+                                  upsample=riders, up_size=(H, W))
+                ups = sel.get("upsampled", ups)
             elif plan.fused_prob:
                 sel = ops.select_depth(hypo, self.depth_interals_ratio[s], self.inverse_depth, feat_cl=plan(cor),
                                        prob_w=plan.prob_w, prob_b=plan.prob_b, want_logits=want_logits)
@@ -440,7 +452,8 @@ class MVS4net(nn.Module):
             outputs.update(st)
         if self.merge_launches:
             coarse = [outputs["stage%d" % (k + 1)] for k in range(min(3, self.num_stage))]
-            ups = ops.upsample_bilinear_multi([st["photometric_confidence"] for st in coarse], H, W)
+            if ups is None:
+                ups = ops.upsample_bilinear_multi([st["photometric_confidence"] for st in coarse], H, W)
             for st, u in zip(coarse, ups):
                 st["photometric_confidence"] = u
             if self.num_stage < 4:
