@@ -609,6 +609,38 @@ int mvster_voxel_thin_emit(const float* points, const unsigned char* colors, lon
                            const int* slot, const long* wg_offsets, unsigned long long* sums, float* out_points,
                            unsigned char* out_colors, int* out_counts, long* out_first, long U, void* stream);
 
+/* ---- cloud-to-cloud nearest distances and scan scores (csrc/geo_nn.hip, csrc/nn_math.h) ---- */
+
+/* The grid of a cloud from what mvster_voxel_thin_insert(points, M, cell, ...) left in first / slot / wg_offsets (the cells
+ * are the voxels of edge `cell`).  ncells = the capacity of counts [ncells] int32 and starts [ncells + 1] int64: the
+ * occupied cells U the caller read back, or M without a read-back.  Afterwards first [table_slots] holds the dense cell id
+ * of every occupied slot (cells in the order of their first point), slot [M] a point's cell id (-1: invalid point), starts
+ * the first record of every cell with starts[ncells] = the valid points, and records [M] the valid points in cell order as
+ * 16-byte records (x, y, z as float32 bits, the point's index as int32).  The order inside a cell may differ between
+ * runs.  local [M] int32 is scratch.  MVSTER_ERR_SHAPE for M outside 1 .. 2^29 or ncells outside 1 .. M.  Five launches. */
+int mvster_cloud_grid_build(const float* points, long M, int* first, int* slot, const long* wg_offsets, int* counts, int* local,
+                            long* starts, long ncells, void* records, void* stream);
+
+/* Nearest target of every query up to max_dist (the definition: csrc/nn_math.h).  The queries come as the grid of their own
+ * cloud: qrecords (NULL where it has no valid point) / qcell (= slot) / qtotal (= starts + ncells of that grid), Q its
+ * points; the target as keys /
+ * cell_of_slot (= first) / starts / records with ncells cells and nrecords records (0 cells: every valid query gets +inf).
+ * Both grids must have been built with this `cell`; cell >= max_dist / 15.  Per query, at its original position: dist2 fp64
+ * = the smallest d2 <= max_dist^2 over the valid targets, dist = (float)sqrt(d2), index = that target's index, the smallest
+ * among equal d2; +inf / +inf / -1 without a candidate, NaN / NaN / -1 for an invalid query.  One launch, no atomics: the
+ * result depends neither on the grid nor on the run.  Every hash probe loop runs at most table_slots iterations. */
+int mvster_cloud_nn_query(const void* qrecords, const int* qcell, const long* qtotal, long Q, const unsigned long long* keys,
+                          const int* cell_of_slot, long table_slots, const long* starts, const void* records, long ncells,
+                          long nrecords, float max_dist, float cell, float* dist, double* dist2, long* index, void* stream);
+
+/* Rows of `partial` for Q distances; MVSTER_ERR_SHAPE for Q outside 1 .. 2^29. */
+int mvster_cloud_score_slots(long Q);
+
+/* out [4] float64 over dist [Q]: the values that are not NaN, those <= max_dist, those < tau (0 <= tau <= max_dist) and the
+ * fp64 sum of those <= max_dist.  partial [slots, 4] float64 (scratch): one row per workgroup, summed in row order -- no
+ * atomics, two runs give the same bytes.  Two launches. */
+int mvster_cloud_score(const float* dist, long Q, float max_dist, float tau, double* partial, double* out, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

@@ -94,6 +94,10 @@ SIGNATURES = {
     "mvster_voxel_thin_blocks": [_l],
     "mvster_voxel_thin_insert": [_f, _l, _fl, _f, _f, _l, _f, _f, _f, _f],
     "mvster_voxel_thin_emit": [_f, _f, _l, _fl, _i] + [_f] * 8 + [_l, _f],
+    "mvster_cloud_grid_build": [_f, _l, _f, _f, _f, _f, _f, _f, _l, _f, _f],
+    "mvster_cloud_nn_query": [_f, _f, _f, _l, _f, _f, _l, _f, _f, _l, _l, _fl, _fl, _f, _f, _f, _f],
+    "mvster_cloud_score_slots": [_l],
+    "mvster_cloud_score": [_f, _l, _fl, _fl, _f, _f, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

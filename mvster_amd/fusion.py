@@ -336,6 +336,226 @@ def thin_points(points, colors, voxel_size, reduce="mean", table_slots=None):
     return dict(out, dropped=dropped)
 
 
+MAX_CLOUD_POINTS = 1 << 29              # as in thin_points: the grid of a cloud is built on the thinning's table
+MIN_CELLS_PER_MAX_DIST = 15             # cell >= max_dist / 15: at most 17 shells per query (csrc/nn_math.h)
+
+
+def _check_length(what, name, value):
+    """A length whose float32 value is finite and > 0 -> that value as a Python float."""
+    try:
+        with np.errstate(over="ignore"):
+            v = float(np.float32(value))
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: %s must be a number, not %r" % (what, name, value)) from None
+    if not (np.isfinite(v) and v > 0):
+        raise RuntimeError("%s: %s must be finite and > 0 as a float32, not %r" % (what, name, value))
+    return v
+
+
+def _check_max_dist_cell(what, max_dist, cell):
+    """-> (max_dist, cell) as float32 values; cell defaults to float32(max_dist / 4) and must be >= max_dist / 15."""
+    md = _check_length(what, "max_dist", max_dist)
+    c = _check_length(what, "cell", md / 4 if cell is None else cell)
+    if not c >= md / MIN_CELLS_PER_MAX_DIST:
+        raise RuntimeError("%s: cell must be >= max_dist / %d = %r, not %r" % (what, MIN_CELLS_PER_MAX_DIST,
+                                                                                md / MIN_CELLS_PER_MAX_DIST, cell))
+    return md, c
+
+
+def _check_cloud(what, name, points):
+    if not isinstance(points, torch.Tensor):
+        raise RuntimeError("%s: %s must be a torch tensor (on the GPU) or a CloudGrid, not %s" % (what, name, type(points).__name__))
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise RuntimeError("%s: %s must be [M,3] float32, not %s %s" % (what, name, tuple(points.shape), points.dtype))
+    if points.shape[0] > MAX_CLOUD_POINTS:
+        raise RuntimeError("%s: at most 2^29 points, not %d in %s" % (what, points.shape[0], name))
+
+
+class CloudGrid:
+    """The uniform hash grid of a cloud: ``points`` [M,3] float32 on the GPU, binned into cells of edge
+    ``cell`` (its float32 value; finite, > 0).  Built once and reused: a ground-truth cloud is scored against many clouds, and
+    ``nearest_distances`` / ``score_clouds`` take a CloudGrid wherever they take a cloud, as the query (its cell order is the
+    order the queries are handled in) and as the target.  Points with a NaN or infinite coordinate, or beyond 2^20 cells from the
+    origin on an axis, take no part: ``dropped`` counts them.  The cells are the voxels of ``thin_points``: the same table
+    (``mvster_voxel_thin_insert``), then ``mvster_cloud_grid_build``.  One host synchronisation (the occupied cells, ``dropped``
+    and the table's status in one copy).  ``table_slots`` as in ``thin_points``; nothing computed from the grid depends on it.
+    No CPU fallback."""
+
+    def __init__(self, points, cell, table_slots=None, _what="CloudGrid", _name="points", _read_back=True):
+        self.cell = _check_length(_what, "cell", cell)
+        _check_cloud(_what, _name, points)
+        M = self.M = points.shape[0]
+        slots = thin_slots(M) if table_slots is None else table_slots
+        if not isinstance(slots, int) or slots < thin_slots(M) or slots & (slots - 1) or slots > 1 << 30:
+            raise RuntimeError("%s: table_slots must be a power of two, >= max(64, 2 * M) = %d and <= 2^30, not %r" %
+                               (_what, max(64, 2 * M), table_slots))
+        if not points.is_cuda:
+            raise RuntimeError("mvster_amd.fusion.%s runs on MI355X only: %s must be a tensor on the GPU (there is no CPU "
+                               "fallback)" % (_what, _name))
+        dev = self.device = points.device
+        self.points, self.slots = points.contiguous(), slots
+        # (an empty cloud's table holds vox::kEmpty everywhere; any other is filled by mvster_voxel_thin_insert)
+        self.keys = torch.full((slots,), -1, device=dev, dtype=torch.int64) if M == 0 else torch.empty(slots, device=dev, dtype=torch.int64)
+        self.cell_of_slot = torch.empty(slots, device=dev, dtype=torch.int32)
+        self.cell_of_point = torch.empty(M, device=dev, dtype=torch.int32)
+        self.starts = torch.zeros(1, device=dev, dtype=torch.int64)
+        self.records = torch.empty(0, 4, device=dev, dtype=torch.int32)
+        self.ncells, self.dropped = 0, 0
+        if M == 0:
+            return
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            nblk = lib.mvster_voxel_thin_blocks(M)
+            _lib.check(min(nblk, 0), "voxel_thin_blocks")
+            wg_counts = torch.empty(nblk, device=dev, dtype=torch.int32)
+            wg_offsets = torch.empty(nblk + 3, device=dev, dtype=torch.int64)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = lib.mvster_voxel_thin_insert(self.points.data_ptr(), M, self.cell, self.keys.data_ptr(), self.cell_of_slot.data_ptr(),
+                                              slots, self.cell_of_point.data_ptr(), wg_counts.data_ptr(), wg_offsets.data_ptr(),
+                                              stream)
+            _lib.check(rc, "voxel_thin_insert")
+            if _read_back:
+                U, self.dropped, status = wg_offsets[nblk:].tolist()             # the one host sync
+                if status:
+                    raise RuntimeError("%s: a point found no slot in a table of %d slots for %d points" % (_what, slots, M))
+                if U == 0:                                                       # every point invalid: cell_of_point is all -1
+                    return
+            else:                                                                # queries: M bounds the cells, nothing is read
+                U, self.dropped = M, wg_offsets[nblk + 1]
+            counts = torch.empty(U, device=dev, dtype=torch.int32)
+            local = torch.empty(M, device=dev, dtype=torch.int32)
+            self.starts = torch.empty(U + 1, device=dev, dtype=torch.int64)
+            self.records = torch.empty(M - (self.dropped if _read_back else 0), 4, device=dev, dtype=torch.int32)
+            rc = lib.mvster_cloud_grid_build(self.points.data_ptr(), M, self.cell_of_slot.data_ptr(), self.cell_of_point.data_ptr(),
+                                             wg_offsets.data_ptr(), counts.data_ptr(), local.data_ptr(), self.starts.data_ptr(), U,
+                                             self.records.data_ptr(), stream)
+            _lib.check(rc, "cloud_grid_build")
+            self.ncells = U
+
+    def __len__(self):
+        return self.M
+
+
+def _as_grid(what, name, cloud, cell, table_slots=None, read_back=True):
+    """A cloud given as a tensor or as a CloudGrid -> a CloudGrid of edge ``cell``."""
+    if isinstance(cloud, CloudGrid):
+        if cloud.cell != cell:
+            raise RuntimeError("%s: the CloudGrid given as %s has cell %r, not the cell %r of this call" % (what, name, cloud.cell, cell))
+        return cloud
+    return CloudGrid(cloud, cell, table_slots, _what=what, _name=name, _read_back=read_back)
+
+
+def _nearest(what, query, target, max_dist, cell, table_slots, read_back_query):
+    md = _check_length(what, "max_dist", max_dist)
+    if cell is None and isinstance(target, CloudGrid):
+        cell = target.cell
+    elif cell is None and isinstance(query, CloudGrid):
+        cell = query.cell
+    md, c = _check_max_dist_cell(what, md, cell)
+    for name, cloud in (("query", query), ("target", target)):                  # both before either grid is built
+        if not isinstance(cloud, CloudGrid):
+            _check_cloud(what, name, cloud)
+    tg = _as_grid(what, "target", target, c, table_slots)
+    qg = _as_grid(what, "query", query, c, None, read_back_query)
+    if qg.device != tg.device:
+        raise RuntimeError("%s: query and target must be on one GPU, not %s and %s" % (what, qg.device, tg.device))
+    dev, Q = qg.device, qg.M
+    out = dict(dist=torch.empty(Q, device=dev, dtype=torch.float32), dist2=torch.empty(Q, device=dev, dtype=torch.float64),
+               index=torch.empty(Q, device=dev, dtype=torch.int64), dropped_query=qg.dropped, dropped_target=tg.dropped)
+    if Q == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _lib.load().mvster_cloud_nn_query(
+            qg.records.data_ptr(), qg.cell_of_point.data_ptr(), qg.starts.data_ptr() + 8 * (qg.starts.numel() - 1), Q,
+            tg.keys.data_ptr(), tg.cell_of_slot.data_ptr(), tg.slots, tg.starts.data_ptr(), tg.records.data_ptr(), tg.ncells,
+            tg.records.shape[0], md, c, out["dist"].data_ptr(), out["dist2"].data_ptr(), out["index"].data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "cloud_nn_query")
+    return out
+
+
+def nearest_distances(query, target, max_dist, cell=None, table_slots=None):
+    """For every point of ``query`` its nearest point of ``target`` up to ``max_dist``, on the GPU (defined
+    exactly in mvster_amd/csrc/nn_math.h): ``query`` [Q,3] and ``target`` [M,3] float32 tensors on the GPU, or either as a
+    ``CloudGrid`` (built once, reused).  In fp64, d2 = (dx*dx + dy*dy) + dz*dz; a query's candidates are the valid targets with
+    d2 <= max_dist^2 (``max_dist`` at its float32 value; finite, > 0) and its result the candidate with the smallest
+    (d2, index).  -> dict of GPU tensors at the query's positions: ``dist2`` [Q] float64 = d2, ``dist`` [Q] float32 =
+    (float)sqrt(d2), ``index`` [Q] int64 into the target as given; +inf / +inf / -1 without a candidate, NaN / NaN / -1 for an
+    invalid query (a NaN or infinite coordinate, or beyond 2^20 cells from the origin); invalid targets take no part.
+    ``dropped_target`` (int) and ``dropped_query`` count the invalid points; ``dropped_query`` is an int for a CloudGrid and a
+    0-dim int64 tensor on the GPU for a tensor, whose binning synchronises nothing.  ``cell``: the edge of the search grid,
+    default float32(max_dist / 4) or the CloudGrid's; >= max_dist / 15.  The result depends neither on ``cell`` (but through
+    which points are valid), nor on ``table_slots`` (the target's table, as in ``thin_points``), nor on the run.  An empty or
+    entirely invalid target gives every valid query +inf / -1.  One host synchronisation where the target is a tensor (its
+    grid), none where it is a CloudGrid.  No CPU fallback."""
+    return _nearest("nearest_distances", query, target, max_dist, cell, table_slots, False)
+
+
+def _check_tau(what, tau, md):
+    if tau is None:
+        return None
+    t = _check_length(what, "tau", tau)
+    if not t <= md:
+        raise RuntimeError("%s: tau must be <= max_dist = %r, not %r" % (what, md, tau))
+    return t
+
+
+def score_clouds(pred, gt, max_dist, tau=None, cell=None):
+    """The scores of a predicted cloud against a ground-truth cloud from ``nearest_distances`` both ways.
+    ``pred`` / ``gt``: [N,3] float32 tensors on the GPU or CloudGrids.  -> dict of Python numbers:
+    ``accuracy`` = the mean of pred -> gt ``dist`` over those <= ``max_dist``, ``completeness`` = the same for gt -> pred,
+    ``overall`` = their mean (DTU's three numbers, distances capped by leaving out what is beyond ``max_dist``); with ``tau``
+    (0 < tau <= max_dist) also ``precision`` = the pred points with dist < tau over the valid pred points, ``recall`` = the same
+    for gt -> pred and ``fscore`` = 2PR / (P + R), 0 when P + R = 0 (Tanks and Temples, ETH3D).  An empty mean is NaN.  The raw
+    numbers come along: ``pred_valid`` / ``pred_within`` / ``pred_below_tau`` (counts), ``pred_sum`` (fp64 sum of the dist <=
+    max_dist), the same with ``gt_``, ``dropped_pred``, ``dropped_gt``.  The sums are formed per workgroup and added in a fixed
+    order: two runs give the same bytes.  One read-back of its own, besides the one of each grid it has to build.
+
+    DTU's observability masks and ground plane are NOT applied: those files are not ours to read.  The numbers are the DTU
+    protocol's only for clouds the caller has masked already."""
+    what = "score_clouds"
+    md = _check_length(what, "max_dist", max_dist)
+    t = _check_tau(what, tau, md)
+    if cell is None:
+        cell = next((g.cell for g in (pred, gt) if isinstance(g, CloudGrid)), None)
+    md, c = _check_max_dist_cell(what, md, cell)
+    for name, cloud in (("pred", pred), ("gt", gt)):
+        if not isinstance(cloud, CloudGrid):
+            _check_cloud(what, name, cloud)
+    gp, gg = _as_grid(what, "pred", pred, c), _as_grid(what, "gt", gt, c)
+    ways = (_nearest(what, gp, gg, md, c, None, True), _nearest(what, gg, gp, md, c, None, True))
+    dev = gp.device
+    stats = torch.zeros(2, 4, device=dev, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for w, way in enumerate(ways):
+            Q = way["dist"].shape[0]
+            if Q == 0:
+                continue
+            slots = lib.mvster_cloud_score_slots(Q)
+            _lib.check(min(slots, 0), "cloud_score_slots")
+            partial = torch.empty(slots, 4, device=dev, dtype=torch.float64)
+            rc = lib.mvster_cloud_score(way["dist"].data_ptr(), Q, md, 0.0 if t is None else t, partial.data_ptr(),
+                                        stats[w].data_ptr(), stream)
+            _lib.check(rc, "cloud_score")
+    rows = stats.tolist()                                                        # the one read-back
+    out = dict(dropped_pred=gp.dropped, dropped_gt=gg.dropped)
+    for name, (valid, within, below, total) in zip(("pred", "gt"), rows):
+        out[name + "_valid"], out[name + "_within"], out[name + "_sum"] = int(valid), int(within), total
+        if t is not None:
+            out[name + "_below_tau"] = int(below)
+    nan = float("nan")
+    out["accuracy"] = out["pred_sum"] / out["pred_within"] if out["pred_within"] else nan
+    out["completeness"] = out["gt_sum"] / out["gt_within"] if out["gt_within"] else nan
+    out["overall"] = (out["accuracy"] + out["completeness"]) / 2
+    if t is not None:
+        P = out["precision"] = out["pred_below_tau"] / out["pred_valid"] if out["pred_valid"] else nan
+        R = out["recall"] = out["gt_below_tau"] / out["gt_valid"] if out["gt_valid"] else nan
+        out["fscore"] = 0.0 if P + R == 0 else 2 * P * R / (P + R)
+    return out
+
+
 def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=None, rel_thres=None,
                device=None, scratch_budget=SCRATCH_BUDGET, events=None, method="normal", pix_base=PIX_BASE,
                rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean"):
