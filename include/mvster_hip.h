@@ -641,6 +641,44 @@ int mvster_cloud_score_slots(long Q);
  * atomics, two runs give the same bytes.  Two launches. */
 int mvster_cloud_score(const float* dist, long Q, float max_dist, float tau, double* partial, double* out, void* stream);
 
+/* ---- the DTU evaluation protocol (csrc/geo_eval.hip, csrc/eval_math.h) ---- */
+
+/* state [M] int32 of the point reduction: 0 (undecided) for a valid point -- vox::point_key(p, dst) accepts it -- and 2
+ * (dropped) for an invalid one; invalid [1] uint64 = the invalid points (zeroed here, one integer atomic per wave).
+ * MVSTER_ERR_SHAPE for M outside 1 .. 2^29 or a dst that is not finite and > 0.  Two launches. */
+int mvster_eval_reduce_init(const float* points, long M, float dst, int* state, unsigned long long* invalid, void* stream);
+
+/* nrounds (1 .. 64) rounds of the reduction over the grid of the cloud at cell = cell_factor * dst (records [nrecords], keys /
+ * cell_of_slot [table_slots], starts [ncells + 1] as mvster_cloud_grid_build left them); cell_factor 2 searches the 3 x 3 x 3
+ * cells around a point's own, cell_factor 1 the 5 x 5 x 5 (csrc/eval_math.h proves both); anything else, or a cell that is not
+ * finite, is MVSTER_ERR_SHAPE.  Point i has the priority (key_i, i): key_i = splitmix64(i, seed) (seed >= 0) where priority is
+ * NULL, else priority [M] int64 in signed order.  In a round every undecided point looks at the points with d2 <= dst^2 and a
+ * smaller priority: one of them kept (state 1) -> dropped (2); none kept and none undecided -> kept; otherwise unchanged.
+ * States are read and written in place with relaxed atomics, each written once.  counts [nrounds] uint64: the points left
+ * undecided after each round (zeroed here, one integer atomic per wave).  1 + nrounds launches; every hash probe loop runs at
+ * most table_slots iterations. */
+int mvster_eval_reduce_rounds(const void* records, long nrecords, const unsigned long long* keys, const int* cell_of_slot,
+                              long table_slots, const long* starts, long ncells, float dst, int cell_factor, const long* priority,
+                              long seed, long M, int* state, unsigned long long* counts, int nrounds, void* stream);
+
+/* flags [N] uint8 of points [N,3]: bit 0 = in_obs_mask, bit 1 = above_plane, bit 2 = covered (csrc/eval_math.h), each only where
+ * `which` (1 .. 7) has the bit.  mask [S1,S2,S3] uint8, C-contiguous (may be NULL without bit 0); params [12] float64 on the
+ * device = BB1 (3), BB2 (3), Res, max_block, P (4).  counts [3] uint64 = the points with each bit (zeroed here, integer
+ * atomics).  Two launches. */
+int mvster_eval_flags(const float* points, long N, const unsigned char* mask, long S1, long S2, long S3, const double* params,
+                      int which, unsigned char* flags, unsigned long long* counts, void* stream);
+
+/* Rows of `partial` for N distances; MVSTER_ERR_SHAPE for N outside 1 .. 2^29. */
+int mvster_eval_stats_slots(long N);
+
+/* out [4] float64 = n, mean, var, median of d = sqrt(dist2 [N]) over the selected points: (flags[i] & need) == need, dist2
+ * finite and d < max_dist (strict).  mean and var (second pass, / (n - 1)) from per-workgroup partials added in slot order;
+ * the median from an exact radix selection of the two middle dist2 over their bit patterns (8 passes of 8 bits, integer
+ * histograms).  n = 0 gives NaN, NaN, NaN.  Scratch: partial [slots, 2] float64, hist [8 * 2 * 256] uint32, work [6] uint64.
+ * No floating-point atomics: two runs give the same bytes.  20 launches. */
+int mvster_eval_stats(const double* dist2, const unsigned char* flags, long N, int need, float max_dist, double* partial,
+                      unsigned* hist, unsigned long long* work, double* out, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

@@ -98,6 +98,11 @@ SIGNATURES = {
     "mvster_cloud_nn_query": [_f, _f, _f, _l, _f, _f, _l, _f, _f, _l, _l, _fl, _fl, _f, _f, _f, _f],
     "mvster_cloud_score_slots": [_l],
     "mvster_cloud_score": [_f, _l, _fl, _fl, _f, _f, _f],
+    "mvster_eval_reduce_init": [_f, _l, _fl, _f, _f, _f],
+    "mvster_eval_reduce_rounds": [_f, _l, _f, _f, _l, _f, _l, _fl, _i, _f, _l, _l, _f, _f, _i, _f],
+    "mvster_eval_flags": [_f, _l, _f, _l, _l, _l, _f, _i, _f, _f, _f],
+    "mvster_eval_stats_slots": [_l],
+    "mvster_eval_stats": [_f, _f, _l, _i, _fl, _f, _f, _f, _f, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

@@ -512,7 +512,8 @@ def score_clouds(pred, gt, max_dist, tau=None, cell=None):
     order: two runs give the same bytes.  One read-back of its own, besides the one of each grid it has to build.
 
     DTU's observability masks and ground plane are NOT applied: those files are not ours to read.  The numbers are the DTU
-    protocol's only for clouds the caller has masked already."""
+    protocol's only for clouds the caller has masked already.  The whole protocol -- point reduction, masks, plane, median and
+    variance -- is ``mvster_amd.dtu_eval.evaluate_dtu_scan``."""
     what = "score_clouds"
     md = _check_length(what, "max_dist", max_dist)
     t = _check_tau(what, tau, md)
