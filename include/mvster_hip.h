@@ -679,6 +679,47 @@ int mvster_eval_stats_slots(long N);
 int mvster_eval_stats(const double* dist2, const unsigned char* flags, long N, int need, float max_dist, double* partial,
                       unsigned* hist, unsigned long long* work, double* out, void* stream);
 
+/* ---- the Tanks and Temples evaluation protocol (csrc/geo_reg.hip, csrc/reg_math.h) ---- */
+
+/* Tiles of 256 points of a cloud of N points: the length of wg_counts; wg_offsets holds one more.  MVSTER_ERR_SHAPE for N
+ * outside 1 .. 2^29. */
+int mvster_reg_blocks(long N);
+
+/* out [N,3] float32 = (float)(T p) for points [N,3] float32: T [12] float64 ON THE HOST (read before the call returns) = the
+ * first three rows of a 4 x 4 matrix, q_a = ((T[4a] x + T[4a+1] y) + T[4a+2] z) + T[4a+3] in fp64.  One launch. */
+int mvster_reg_transform(const float* points, long N, const double* T, float* out, void* stream);
+
+/* flags [N] uint8 = 1 where q = T p (T as above, on the host; NULL: q = p) lies inside the crop volume: volume [2 + 2 P]
+ * float64 on the device = axis_min, axis_max, then (u, v) of the P polygon vertices; axis 0 / 1 / 2 = the orthogonal axis
+ * X / Y / Z (csrc/reg_math.h has the rule).  wg_counts [blocks] int32 (scratch); wg_offsets [blocks + 1] int64 = the exclusive
+ * scan of the kept points per tile, its last word the kept count: the caller's one read-back.  max_grid: workgroups at most,
+ * 0 for the default (2048), never more.  MVSTER_ERR_SHAPE before any launch for P outside 3 .. 1024, an axis outside 0 .. 2, N
+ * outside 1 .. 2^29.  Two launches, no atomics. */
+int mvster_reg_crop_flags(const float* points, long N, const double* T, const double* volume, int P, int axis, int max_grid,
+                          unsigned char* flags, int* wg_counts, long* wg_offsets, void* stream);
+
+/* The kept points in the input's order, with flags / wg_offsets as mvster_reg_crop_flags left them and K the kept count read
+ * back: out_points [K,3] = (float)q (the input's bits where T is NULL), out_index [K] int64 = the position in the input,
+ * out_colors [K,3] uint8 where colors is not NULL.  K = 0 launches nothing.  One launch. */
+int mvster_reg_crop_emit(const float* points, const unsigned char* colors, long N, const double* T, const unsigned char* flags,
+                         const long* wg_offsets, long K, int max_grid, float* out_points, unsigned char* out_colors,
+                         long* out_index, void* stream);
+
+/* Rows of `partial` for Q source points; MVSTER_ERR_SHAPE for Q outside 1 .. 2^29. */
+int mvster_reg_sum_rows(long Q);
+
+/* out [18] float64 over the source points i with 0 <= index[i] < M: n, sum d2, sum s (3), sum t (3), sum s.s, sum t_a s_b (9,
+ * row a, column b); s = source [Q,3] float32 (already moved), t = target [M,3] float32 at index[i], d2 = dist2[i], index /
+ * dist2 as mvster_cloud_nn_query gave them.  partial [rows, 18] float64 (scratch): one row per workgroup, added in row order.
+ * No atomics: two runs give the same bytes.  Two launches. */
+int mvster_reg_sums(const float* source, const long* index, const double* dist2, long Q, const float* target, long M,
+                    double* partial, double* out, void* stream);
+
+/* hist [bins] uint64 = np.histogram(dist, edges)[0]: dist [N] float32, edges [bins + 1] float64 on the device, non-decreasing;
+ * edges[k] <= d < edges[k+1], the last bin closed on the right; NaN and values outside the edges are not counted.  1 <= bins <=
+ * 4096.  hist is zeroed here.  Integer atomics (an LDS histogram per workgroup).  Two launches. */
+int mvster_reg_histogram(const float* dist, long N, const double* edges, int bins, unsigned long long* hist, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

@@ -103,6 +103,13 @@ SIGNATURES = {
     "mvster_eval_flags": [_f, _l, _f, _l, _l, _l, _f, _i, _f, _f, _f],
     "mvster_eval_stats_slots": [_l],
     "mvster_eval_stats": [_f, _f, _l, _i, _fl, _f, _f, _f, _f, _f],
+    "mvster_reg_blocks": [_l],
+    "mvster_reg_transform": [_f, _l, _f, _f, _f],
+    "mvster_reg_crop_flags": [_f, _l, _f, _f, _i, _i, _i, _f, _f, _f, _f],
+    "mvster_reg_crop_emit": [_f, _f, _l, _f, _f, _f, _l, _i, _f, _f, _f, _f],
+    "mvster_reg_sum_rows": [_l],
+    "mvster_reg_sums": [_f, _f, _f, _l, _f, _l, _f, _f, _f],
+    "mvster_reg_histogram": [_f, _l, _f, _i, _f, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
