@@ -720,6 +720,53 @@ int mvster_reg_sums(const float* source, const long* index, const double* dist2,
  * 4096.  hist is zeroed here.  Integer atomics (an LDS histogram per workgroup).  Two launches. */
 int mvster_reg_histogram(const float* dist, long N, const double* edges, int bins, unsigned long long* hist, void* stream);
 
+/* ---- cleaning a fused cloud: k nearest, outlier filters, normals (csrc/geo_knn.hip, csrc/knn_math.h) ---- */
+
+/* The k nearest targets (1 <= k <= 32) of every query up to max_dist, in ascending (d2, index) order (the definition:
+ * csrc/knn_math.h); the grids and max_dist / cell as for mvster_cloud_nn_query.  exclude_self (0 / 1; needs Q == M, the target's
+ * points): the target whose index is the query's position is no candidate.  At the query's position: dist2 [Q,k] float64,
+ * index [Q,k] int64, count [Q] int32 = min(k, candidates); unfilled places +inf / -1; an invalid query NaN / -1 / 0.  Every
+ * check comes before the launch (MVSTER_ERR_SHAPE / MVSTER_ERR_NULL).  One launch, no atomics. */
+int mvster_cloud_knn_query(const void* qrecords, const int* qcell, const long* qtotal, long Q, const unsigned long long* keys,
+                           const int* cell_of_slot, long table_slots, const long* starts, const void* records, long ncells,
+                           long nrecords, float max_dist, float cell, int k, int exclude_self, long M, double* dist2, long* index,
+                           int* count, void* stream);
+
+/* The same search of a cloud's grid (records / cell_of_point (= slot) / keys / cell_of_slot / starts of M points with ncells
+ * cells and nrecords records) against itself with exclude_self, without the lists in memory: count [M] int32 and mean [M]
+ * float64 = (the sum of sqrt(d2) in list order) / k, +inf where count < k, NaN for an invalid point.  One launch. */
+int mvster_cloud_knn_mean(const void* records, const int* cell_of_point, long M, const unsigned long long* keys,
+                          const int* cell_of_slot, long table_slots, const long* starts, long ncells, long nrecords, float max_dist,
+                          float cell, int k, int* count, double* mean, void* stream);
+
+/* The same search, then knn::normal per point: normals [M,3] float32 and valid [M] uint8 (zeros and 0 with fewer than two
+ * neighbours or an invalid point).  points [M,3] = the cloud of the grid; toward [M,3] float32 or NULL (raw sign).  One launch. */
+int mvster_cloud_knn_normals(const void* records, const int* cell_of_point, long M, const unsigned long long* keys,
+                             const int* cell_of_slot, long table_slots, const long* starts, long ncells, long nrecords,
+                             float max_dist, float cell, int k, const float* points, const float* toward, float* normals,
+                             unsigned char* valid, void* stream);
+
+/* neighbours [M] int32 = the valid points within `radius` of every point of the grid's cloud but the point itself (0 for an
+ * invalid point): no list, every shell up to R.  One launch. */
+int mvster_cloud_radius_count(const void* records, const int* cell_of_point, long M, const unsigned long long* keys,
+                              const int* cell_of_slot, long table_slots, const long* starts, long ncells, long nrecords,
+                              float radius, float cell, int* neighbours, void* stream);
+
+/* Rows of `partial` for M means; MVSTER_ERR_SHAPE for M outside 1 .. 2^29. */
+int mvster_cloud_knn_stats_rows(long M);
+
+/* stats [0 .. 3] float64 = n, mu, sigma, threshold = mu + std_ratio * sigma over the means that take part (not +inf, not NaN):
+ * two passes, partial [rows, 2] float64 (scratch), one row per workgroup, added in row order (csrc/knn_math.h has the order).
+ * No atomics: two runs give the same bytes.  std_ratio finite.  Four launches. */
+int mvster_cloud_knn_stats(const double* mean, long M, double std_ratio, double* partial, double* stats, void* stream);
+
+/* flags [M] uint8 of the kept points, wg_counts [tiles] int32 and wg_offsets [tiles + 1] int64 over tiles of 256 points
+ * (tiles = mvster_reg_blocks(M)) exactly as mvster_reg_crop_flags leaves them, so mvster_reg_crop_emit (T = NULL) compacts in
+ * cloud order.  mean != NULL: keep iff mean takes part and mean <= stats[3]; stats[4] = the kept count as a float64 (one
+ * read-back for all five).  mean == NULL: keep iff cell_of_point >= 0 and neighbours >= nb_points (>= 1).  No atomics. */
+int mvster_cloud_keep_flags(const int* cell_of_point, const int* neighbours, int nb_points, const double* mean, double* stats,
+                            long M, unsigned char* flags, int* wg_counts, long* wg_offsets, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

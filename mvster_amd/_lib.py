@@ -110,6 +110,13 @@ SIGNATURES = {
     "mvster_reg_sum_rows": [_l],
     "mvster_reg_sums": [_f, _f, _f, _l, _f, _l, _f, _f, _f],
     "mvster_reg_histogram": [_f, _l, _f, _i, _f, _f],
+    "mvster_cloud_knn_query": [_f, _f, _f, _l, _f, _f, _l, _f, _f, _l, _l, _fl, _fl, _i, _i, _l, _f, _f, _f, _f],
+    "mvster_cloud_knn_mean": [_f, _f, _l, _f, _f, _l, _f, _l, _l, _fl, _fl, _i, _f, _f, _f],
+    "mvster_cloud_knn_normals": [_f, _f, _l, _f, _f, _l, _f, _l, _l, _fl, _fl, _i, _f, _f, _f, _f, _f],
+    "mvster_cloud_radius_count": [_f, _f, _l, _f, _f, _l, _f, _l, _l, _fl, _fl, _f, _f],
+    "mvster_cloud_knn_stats_rows": [_l],
+    "mvster_cloud_knn_stats": [_f, _l, ctypes.c_double, _f, _f, _f],
+    "mvster_cloud_keep_flags": [_f, _f, _i, _f, _f, _l, _f, _f, _f, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

@@ -138,12 +138,28 @@ def fuse_views(per_view_results):
     return v
 
 
-def write_ply(filename, vertices):
+PLY_NORMAL_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                    ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
+def write_ply(filename, vertices, normals=None):
     """Binary little-endian PLY with one ``vertex`` element, the file ``PlyData([PlyElement.describe(v, 'vertex')])
-    .write(f)`` produces for the array above (test_mvs4.py:420-421)."""
+    .write(f)`` produces for the array above (test_mvs4.py:420-421).  ``normals`` [M,3] (array or tensor; default None: the
+    same bytes as ever): the vertex element is x y z nx ny nz red green blue, the order Open3D writes."""
     v = np.ascontiguousarray(vertices, dtype=PLY_VERTEX_DTYPE)
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-              "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(v))
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        n = _np32(normals)
+        if n.shape != (len(v), 3):
+            raise RuntimeError("write_ply: normals must be [M,3] with the M of vertices (%d), not %s" % (len(v), n.shape))
+        w = np.empty(len(v), dtype=PLY_NORMAL_VERTEX_DTYPE)
+        for name in PLY_VERTEX_DTYPE.names:
+            w[name] = v[name]
+        w["nx"], w["ny"], w["nz"] = n[:, 0], n[:, 1], n[:, 2]
+        v = w
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v) + props +
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
     with open(filename, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(v.tobytes())
@@ -200,13 +216,17 @@ class SceneResult(dict):
     ``geo_mask``, ``final_mask``, ``geo_mask_sum``, ``depth_est_averaged``; with ``method="dynamic"`` also ``geo_level``)
     plus ``vertices()``."""
 
-    def vertices(self, thinned=False):
+    def vertices(self, thinned=False, final=False):
         """The structured vertex array of filter_depth (test_mvs4.py:409-418) on the host, ready for ``write_ply``;
-        ``thinned``: of the voxel-thinned cloud (``fuse_scene(voxel_size=...)``), an error if there is none."""
+        ``thinned``: of the voxel-thinned cloud (``fuse_scene(voxel_size=...)``), an error if there is none; ``final``: of the
+        cleaned cloud (``fuse_scene(outliers=..., normals=...)``), an error if there is none."""
         if thinned and "thin_points" not in self:
             raise RuntimeError("SceneResult.vertices(thinned=True): this result holds no thinned cloud (fuse_scene was "
                                "called without voxel_size)")
-        pts, cols = (self[("thin_" if thinned else "") + k].cpu().numpy() for k in ("points", "colors"))
+        if final and "final_points" not in self:
+            raise RuntimeError("SceneResult.vertices(final=True): this result holds no cleaned cloud (fuse_scene was called "
+                               "without outliers and normals)")
+        pts, cols = (self[("final_" if final else "thin_" if thinned else "") + k].cpu().numpy() for k in ("points", "colors"))
         v = np.empty(len(pts), dtype=PLY_VERTEX_DTYPE)
         v["x"], v["y"], v["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
         v["red"], v["green"], v["blue"] = cols[:, 0], cols[:, 1], cols[:, 2]
@@ -557,9 +577,288 @@ def score_clouds(pred, gt, max_dist, tau=None, cell=None):
     return out
 
 
+# ---- cleaning a fused cloud: k nearest, outlier filters, normals --------------------------------------
+
+MAX_K = 32                              # knn::kMaxK of csrc/knn_math.h
+
+RadiusOutliers = collections.namedtuple("RadiusOutliers", "radius nb_points")
+StatisticalOutliers = collections.namedtuple("StatisticalOutliers", "k std_ratio max_dist")
+Normals = collections.namedtuple("Normals", "k max_dist")
+
+
+def _check_k(what, k, name="k", hi=MAX_K):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= hi:
+        raise RuntimeError("%s: %s must be an integer in 1 .. %d, not %r" % (what, name, hi, k))
+    return int(k)
+
+
+def _check_ratio(what, std_ratio, name="std_ratio"):
+    try:
+        r = float(std_ratio)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: %s must be a number, not %r" % (what, name, std_ratio)) from None
+    if not np.isfinite(r):
+        raise RuntimeError("%s: %s must be finite, not %r" % (what, name, std_ratio))
+    return r
+
+
+def _self_grid(what, points, max_dist, cell, name="max_dist"):
+    """The checks every operation on one cloud shares, then its grid -> (grid, max_dist, cell)."""
+    md = _check_length(what, name, max_dist)
+    if cell is None and isinstance(points, CloudGrid):
+        cell = points.cell
+    try:
+        md, c = _check_max_dist_cell(what, md, cell)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace("max_dist", name)) from None
+    if not isinstance(points, CloudGrid):
+        _check_cloud(what, "points", points)
+    return _as_grid(what, "points", points, c), md, c
+
+
+def _grid_args(g):
+    """A cloud's grid as the kernels of geo_knn.hip take it, searched against itself."""
+    return (g.records.data_ptr(), g.cell_of_point.data_ptr(), g.M, g.keys.data_ptr(), g.cell_of_slot.data_ptr(), g.slots,
+            g.starts.data_ptr(), g.ncells, g.records.shape[0])
+
+
+def nearest_neighbors(query, target, k, max_dist, cell=None, table_slots=None, exclude_self=False):
+    """For every point of ``query`` its ``k`` (1 .. 32) nearest points of ``target`` up to ``max_dist``, on the GPU (DESIGN.md
+    section 4.20; defined exactly in mvster_amd/csrc/knn_math.h).  Clouds, ``max_dist``, ``cell``, ``table_slots`` and point
+    validity as in ``nearest_distances``.  A query's candidates are the valid targets with d2 <= max_dist^2; with
+    ``exclude_self`` (needs as many queries as targets) the target whose index is the query's own position is left out -- only
+    that one, a duplicate with another index stays.  -> dict of GPU tensors: ``dist2`` [Q,k] float64 and ``index`` [Q,k] int64,
+    the first min(k, candidates) candidates in ascending (d2, index) order, unfilled places +inf / -1, an invalid query NaN / -1;
+    ``count`` [Q] int32 (0 for an invalid query); ``dropped_query`` / ``dropped_target`` as in ``nearest_distances``.  k = 1
+    gives ``nearest_distances``.  The result depends neither on ``cell``, nor on ``table_slots``, nor on the run.  No CPU
+    fallback."""
+    what = "nearest_neighbors"
+    k = _check_k(what, k)
+    md = _check_length(what, "max_dist", max_dist)
+    if cell is None and isinstance(target, CloudGrid):
+        cell = target.cell
+    elif cell is None and isinstance(query, CloudGrid):
+        cell = query.cell
+    md, c = _check_max_dist_cell(what, md, cell)
+    for name, cloud in (("query", query), ("target", target)):                  # both before either grid is built
+        if isinstance(cloud, CloudGrid):
+            _as_grid(what, name, cloud, c)
+        else:
+            _check_cloud(what, name, cloud)
+    if exclude_self and len(query) != len(target):
+        raise RuntimeError("%s: exclude_self needs as many queries as targets (the same cloud), not %d and %d" %
+                           (what, len(query), len(target)))
+    tg = _as_grid(what, "target", target, c, table_slots)
+    qg = tg if query is target else _as_grid(what, "query", query, c, None, False)
+    if qg.device != tg.device:
+        raise RuntimeError("%s: query and target must be on one GPU, not %s and %s" % (what, qg.device, tg.device))
+    dev, Q = qg.device, qg.M
+    out = dict(dist2=torch.empty(Q, k, device=dev, dtype=torch.float64), index=torch.empty(Q, k, device=dev, dtype=torch.int64),
+               count=torch.empty(Q, device=dev, dtype=torch.int32), dropped_query=qg.dropped, dropped_target=tg.dropped)
+    if Q == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _lib.load().mvster_cloud_knn_query(
+            qg.records.data_ptr(), qg.cell_of_point.data_ptr(), qg.starts.data_ptr() + 8 * (qg.starts.numel() - 1), Q,
+            tg.keys.data_ptr(), tg.cell_of_slot.data_ptr(), tg.slots, tg.starts.data_ptr(), tg.records.data_ptr(), tg.ncells,
+            tg.records.shape[0], md, c, k, 1 if exclude_self else 0, tg.M, out["dist2"].data_ptr(), out["index"].data_ptr(),
+            out["count"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "cloud_knn_query")
+    return out
+
+
+def _compact(g, flags, wg_offsets, kept, colors=None):
+    """The kept points of a grid's cloud in cloud order (mvster_reg_crop_emit) -> (index int64, points, colors or None)."""
+    dev = g.device
+    index = torch.empty(kept, device=dev, dtype=torch.int64)
+    points = torch.empty(kept, 3, device=dev, dtype=torch.float32)
+    cols = torch.empty(kept, 3, device=dev, dtype=torch.uint8) if colors is not None else None
+    if kept:
+        rc = _lib.load().mvster_reg_crop_emit(g.points.data_ptr(), None if colors is None else colors.data_ptr(), g.M, None,
+                                              flags.data_ptr(), wg_offsets.data_ptr(), kept, 0, points.data_ptr(),
+                                              None if cols is None else cols.data_ptr(), index.data_ptr(),
+                                              torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "reg_crop_emit")
+    return index, points, cols
+
+
+def _check_colors(what, points, colors):
+    if colors is None:
+        return None
+    M = len(points)
+    if not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (M, 3) or colors.dtype != torch.uint8:
+        raise RuntimeError("%s: colors must be a [M,3] uint8 tensor with the M of points (%d)" % (what, M))
+    if not colors.is_cuda:
+        raise RuntimeError("%s: colors must be on the GPU of points (there is no CPU fallback)" % what)
+    return colors.contiguous()
+
+
+def radius_outliers(points, radius, nb_points, cell=None, colors=None):
+    """The radius outlier filter on the GPU (PCL's RadiusOutlierRemoval, Open3D's remove_radius_outlier):
+    ``neighbours`` = the valid points within ``radius`` (d2 <= radius^2 in fp64) of a point, the point itself -- its own index,
+    not its duplicates -- left out; a point is kept iff it is valid and has at least ``nb_points`` (an integer >= 1) of them.
+    ``points`` [M,3] float32 on the GPU or a ``CloudGrid``; ``cell`` as in ``nearest_distances`` (default radius / 4).  ->
+    dict: ``keep`` [M] bool, ``neighbours`` [M] int32 (0 for an invalid point), ``index`` [K] int64 (the kept positions, cloud
+    order), ``points`` [K,3] (and ``colors`` [K,3] where ``colors`` [M,3] uint8 is given) on the GPU, ``dropped`` (invalid
+    points).  One read-back of its own (K), besides the grid's.  No atomics: two runs give the same bytes.  No CPU fallback."""
+    what = "radius_outliers"
+    nb = _check_k(what, nb_points, "nb_points", (1 << 31) - 1)
+    colors = _check_colors(what, points, colors)
+    g, r, c = _self_grid(what, points, radius, cell, "radius")
+    dev, M = g.device, g.M
+    keep = torch.zeros(M, device=dev, dtype=torch.uint8)
+    neighbours = torch.zeros(M, device=dev, dtype=torch.int32)
+    kept = 0
+    wg_offsets = None
+    if M:
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.mvster_cloud_radius_count(*_grid_args(g), r, c, neighbours.data_ptr(), stream), "cloud_radius_count")
+            tiles = lib.mvster_reg_blocks(M)
+            _lib.check(min(tiles, 0), "reg_blocks")
+            wg_counts = torch.empty(tiles, device=dev, dtype=torch.int32)
+            wg_offsets = torch.empty(tiles + 1, device=dev, dtype=torch.int64)
+            _lib.check(lib.mvster_cloud_keep_flags(g.cell_of_point.data_ptr(), neighbours.data_ptr(), nb, None, None, M,
+                                                   keep.data_ptr(), wg_counts.data_ptr(), wg_offsets.data_ptr(), stream),
+                       "cloud_keep_flags")
+            kept = int(wg_offsets[tiles])                                        # the one read-back
+    with torch.cuda.device(dev):
+        index, pts, cols = _compact(g, keep, wg_offsets, kept, colors)
+    out = dict(keep=keep.bool(), neighbours=neighbours, index=index, points=pts, dropped=g.dropped)
+    if cols is not None:
+        out["colors"] = cols
+    return out
+
+
+def statistical_outliers(points, k, std_ratio, max_dist, cell=None, colors=None):
+    """The statistical outlier filter on the GPU (PCL's StatisticalOutlierRemoval, Open3D's remove_statistical_outlier, with a
+    search cap; DESIGN.md section 4.20).  A valid point takes part iff it has ``k`` (1 .. 32) other points within ``max_dist``;
+    ``mean`` = the mean distance to its k nearest.  Over the n participants mu and sigma (n - 1 in the denominator; 0 for
+    n < 2) of ``mean``; kept iff it takes part and mean <= ``threshold`` = mu + ``std_ratio`` * sigma.  A point with fewer than k
+    neighbours within ``max_dist`` is isolated: removed, and no part of the statistics.  -> dict: ``keep`` [M] bool, ``mean``
+    [M] float64 (+inf for an isolated point, NaN for an invalid one), ``n`` (int), ``mu``, ``sigma``, ``threshold`` (Python
+    floats), ``index`` / ``points`` (/ ``colors``) of the kept points in cloud order, ``dropped``.  The sums are formed per
+    workgroup and added in a fixed order, no floating-point atomics: two runs give the same bytes.  One read-back of its own
+    (the kept count and the four scalars in one copy), besides the grid's.  No CPU fallback."""
+    what = "statistical_outliers"
+    k = _check_k(what, k)
+    ratio = _check_ratio(what, std_ratio)
+    colors = _check_colors(what, points, colors)
+    g, md, c = _self_grid(what, points, max_dist, cell)
+    dev, M = g.device, g.M
+    keep = torch.zeros(M, device=dev, dtype=torch.uint8)
+    mean = torch.empty(M, device=dev, dtype=torch.float64)
+    nan = float("nan")
+    vals, wg_offsets = [0.0, nan, 0.0, nan, 0.0], None
+    if M:
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            count = torch.empty(M, device=dev, dtype=torch.int32)
+            _lib.check(lib.mvster_cloud_knn_mean(*_grid_args(g), md, c, k, count.data_ptr(), mean.data_ptr(), stream),
+                       "cloud_knn_mean")
+            rows = lib.mvster_cloud_knn_stats_rows(M)
+            _lib.check(min(rows, 0), "cloud_knn_stats_rows")
+            partial = torch.empty(rows, 2, device=dev, dtype=torch.float64)
+            stats = torch.empty(5, device=dev, dtype=torch.float64)
+            _lib.check(lib.mvster_cloud_knn_stats(mean.data_ptr(), M, ratio, partial.data_ptr(), stats.data_ptr(), stream),
+                       "cloud_knn_stats")
+            tiles = lib.mvster_reg_blocks(M)
+            _lib.check(min(tiles, 0), "reg_blocks")
+            wg_counts = torch.empty(tiles, device=dev, dtype=torch.int32)
+            wg_offsets = torch.empty(tiles + 1, device=dev, dtype=torch.int64)
+            _lib.check(lib.mvster_cloud_keep_flags(None, None, 0, mean.data_ptr(), stats.data_ptr(), M, keep.data_ptr(),
+                                                   wg_counts.data_ptr(), wg_offsets.data_ptr(), stream), "cloud_keep_flags")
+            vals = stats.tolist()                                                # the one read-back
+    with torch.cuda.device(dev):
+        index, pts, cols = _compact(g, keep, wg_offsets, int(vals[4]), colors)
+    out = dict(keep=keep.bool(), mean=mean, n=int(vals[0]), mu=vals[1], sigma=vals[2], threshold=vals[3], index=index,
+               points=pts, dropped=g.dropped)
+    if cols is not None:
+        out["colors"] = cols
+    return out
+
+
+def estimate_normals(points, k, max_dist, toward=None, cell=None):
+    """A normal per point on the GPU (defined exactly in mvster_amd/csrc/knn_math.h): the unit
+    eigenvector of the smallest eigenvalue of the covariance of the point and its ``k`` (1 .. 32) nearest other points within
+    ``max_dist``, by a fixed number of cyclic Jacobi sweeps in fp64.  ``toward`` [M,3] float32 (one position per point, e.g.
+    the camera centre it was seen from): the normal is turned so that n . (toward - p) >= 0; without it, or where that product
+    is exactly 0, the component of largest magnitude is positive.  -> dict: ``normals`` [M,3] float32 and ``valid`` [M] bool;
+    a point with fewer than two neighbours, or an invalid one, gets zeros and False.  Nothing is read back besides the grid's
+    read-back.  No CPU fallback."""
+    what = "estimate_normals"
+    k = _check_k(what, k)
+    if toward is not None and (not isinstance(toward, torch.Tensor) or tuple(toward.shape) != (len(points), 3) or
+                               toward.dtype != torch.float32):
+        raise RuntimeError("%s: toward must be a [M,3] float32 tensor with the M of points (%d)" % (what, len(points)))
+    g, md, c = _self_grid(what, points, max_dist, cell)
+    dev, M = g.device, g.M
+    if toward is not None:
+        if toward.device != dev:
+            raise RuntimeError("%s: toward must be on the GPU of points (there is no CPU fallback)" % what)
+        toward = toward.contiguous()
+    normals = torch.zeros(M, 3, device=dev, dtype=torch.float32)
+    valid = torch.zeros(M, device=dev, dtype=torch.uint8)
+    if M:
+        with torch.cuda.device(dev):
+            rc = _lib.load().mvster_cloud_knn_normals(*_grid_args(g), md, c, k, g.points.data_ptr(),
+                                                      None if toward is None else toward.data_ptr(), normals.data_ptr(),
+                                                      valid.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(rc, "cloud_knn_normals")
+    return dict(normals=normals, valid=valid.bool())
+
+
+def _check_clean(what, outliers, normals):
+    """The ``outliers`` / ``normals`` keywords of the scan-level entry points, checked before anything runs."""
+    if outliers is not None:
+        if isinstance(outliers, RadiusOutliers):
+            _check_length(what, "outliers.radius", outliers.radius)
+            _check_k(what, outliers.nb_points, "outliers.nb_points", (1 << 31) - 1)
+        elif isinstance(outliers, StatisticalOutliers):
+            _check_k(what, outliers.k, "outliers.k")
+            _check_ratio(what, outliers.std_ratio, "outliers.std_ratio")
+            _check_length(what, "outliers.max_dist", outliers.max_dist)
+        else:
+            raise RuntimeError("%s: outliers must be None, a RadiusOutliers or a StatisticalOutliers, not %r" % (what, outliers))
+    if normals is not None:
+        if not isinstance(normals, Normals):
+            raise RuntimeError("%s: normals must be None or a Normals, not %r" % (what, normals))
+        _check_k(what, normals.k, "normals.k")
+        _check_length(what, "normals.max_dist", normals.max_dist)
+
+
+def _clean_scene(res, Es, pairs, thinned, outliers, normals):
+    """fuse_scene's last step: the cloud that would be written through the filter, then the normals -> the ``final_*`` keys."""
+    pre = "thin_" if thinned else ""
+    pts, cols = res[pre + "points"], res[pre + "colors"]
+    dev = pts.device
+    out = {}
+    if isinstance(outliers, RadiusOutliers):
+        f = radius_outliers(pts, outliers.radius, outliers.nb_points, colors=cols)
+        out.update(final_radius=float(np.float32(outliers.radius)), final_nb_points=int(outliers.nb_points))
+    elif isinstance(outliers, StatisticalOutliers):
+        f = statistical_outliers(pts, outliers.k, outliers.std_ratio, outliers.max_dist, colors=cols)
+        out.update(("final_" + key, f[key]) for key in ("n", "mu", "sigma", "threshold"))
+    else:
+        f = dict(points=pts, colors=cols, index=torch.arange(len(pts), device=dev, dtype=torch.int64))
+    out.update(final_points=f["points"], final_colors=f["colors"], final_index=f["index"])
+    if normals is not None:
+        # the camera centre -R^T T = inv(E)[:3, 3] of the reference view a point came from (a voxel: of its first point)
+        centres = np.stack([np.linalg.inv(np.asarray(Es[r], np.float64))[:3, 3] for r, _ in pairs]).astype(np.float32)
+        view = torch.repeat_interleave(torch.arange(len(pairs), device=dev), res["counts"].to(dev), output_size=len(res["points"]))
+        if thinned:
+            view = view[res["thin_first"]]
+        toward = torch.from_numpy(centres).to(dev)[view[f["index"]]]
+        nrm = estimate_normals(f["points"], normals.k, normals.max_dist, toward=toward)
+        out.update(final_normals=nrm["normals"], final_normal_valid=nrm["valid"])
+    return out
+
+
 def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=None, rel_thres=None,
                device=None, scratch_budget=SCRATCH_BUDGET, events=None, method="normal", pix_base=PIX_BASE,
-               rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean"):
+               rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean", outliers=None, normals=None):
     """filter_depth (test_mvs4.py:331-421) for a scan whose maps are in memory.  depths / confidences [V,H,W], images
     [V,H,W,3] (uint8, or float 0..1 as ``read_img`` returns it), Ks [V,3,3], Es [V,4,4]: NumPy arrays, tensors or
     sequences of them, indexed by the view numbers in ``pairs`` [(ref_view, [src_view, ...]), ...].  Tensors already on
@@ -581,9 +880,18 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
 
     ``voxel_size`` (default None: nothing changes): the whole cloud, after its chunks are joined, also goes through
     ``thin_points(points, colors, voxel_size, voxel_reduce)`` and the result holds ``thin_points``, ``thin_colors``,
-    ``thin_counts``, ``thin_first`` and ``thin_dropped`` beside the unchanged ``points``, ``colors`` and ``counts``."""
+    ``thin_counts``, ``thin_first`` and ``thin_dropped`` beside the unchanged ``points``, ``colors`` and ``counts``.
+
+    ``outliers`` (a ``RadiusOutliers`` or a ``StatisticalOutliers``) / ``normals`` (a ``Normals``); default None, None: nothing
+    changes.  Otherwise the cloud that would be written -- ``thin_*`` with a ``voxel_size``, else ``points`` / ``colors`` -- goes
+    through ``radius_outliers`` / ``statistical_outliers``, then ``estimate_normals``, and the result additionally holds
+    ``final_points``, ``final_colors``, ``final_index`` (int64, into the cloud it was taken from), the filter's scalars
+    (``final_n``, ``final_mu``, ``final_sigma``, ``final_threshold``, or ``final_radius``, ``final_nb_points``) and, with
+    ``normals``, ``final_normals`` / ``final_normal_valid``: oriented toward the camera centre -R^T T of the reference view a
+    point came from (a voxel: of its first point).  Every other key stays byte-equal."""
     _check_method("fuse_scene", method, pix_thres, rel_thres)
     _check_voxel("fuse_scene", voxel_size, voxel_reduce)
+    _check_clean("fuse_scene", outliers, normals)
     dynamic = method == "dynamic"
     pix_thres = PIX_THRES if pix_thres is None else pix_thres
     rel_thres = REL_THRES if rel_thres is None else rel_thres
@@ -685,20 +993,34 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
         res["geo_level"] = level
     if voxel_size is not None:
         res.update(("thin_" + k, t) for k, t in thin_points(res["points"], res["colors"], voxel_size, voxel_reduce).items())
+    if outliers is not None or normals is not None:
+        res.update(_clean_scene(res, Es, pairs, voxel_size is not None, outliers, normals))
     return res
 
 
+def write_scene_ply(filename, res, thinned=False):
+    """The cloud of a SceneResult as the scan-level entry points write it: the cleaned one (with its normals) where there is
+    one, else the thinned one where ``thinned``, else ``points`` / ``colors``.  -> the vertex array written."""
+    final = "final_points" in res
+    vertices = res.vertices(thinned=thinned, final=final)
+    write_ply(filename, vertices, res["final_normals"].cpu().numpy() if "final_normals" in res else None)
+    return vertices
+
+
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, thres_view=5, device="cuda:0",
-                 filter_method="normal", pix_base=PIX_BASE, rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean"):
+                 filter_method="normal", pix_base=PIX_BASE, rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean",
+                 outliers=None, normals=None):
     """The reference's ``filter_depth`` (test_mvs4.py:331-421; its ``args.conf`` / ``args.thres_view`` are keywords
     here): reads ``pair_folder/pair.txt``, ``scan_folder/cams/{:0>8}_cam.txt`` and ``images/{:0>8}.jpg``,
     ``out_folder/depth_est/{:0>8}.pfm`` and ``confidence/{:0>8}.pfm`` -- every file once --, fuses the scan on the GPU and
     writes ``out_folder/mask/{:0>8}_{photo,geo,final}.png`` (:390-393) and the point cloud ``plyfilename``.
     ``filter_method="dynamic"`` (with ``pix_base`` / ``rel_base``) writes the same files with the masks of dynamic
     consistency checking, see ``fuse_scene``.  With ``voxel_size`` the cloud written and returned is the voxel-thinned one
-    (``thin_points`` with ``voxel_reduce``).  -> the vertex array."""
+    (``thin_points`` with ``voxel_reduce``).  ``outliers`` / ``normals``: as ``fuse_scene``; the cloud written and returned is
+    then the cleaned one, with nx ny nz in the file where normals were asked for.  -> the vertex array."""
     _check_method("filter_depth", filter_method)
     _check_voxel("filter_depth", voxel_size, voxel_reduce)
+    _check_clean("filter_depth", outliers, normals)
     try:
         from PIL import Image
     except ImportError as e:
@@ -718,12 +1040,10 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, th
     res = fuse_scene(depths, confs, images, [c[0] for c in cams], [c[1] for c in cams],
                      [(slot[r], [slot[v] for v in srcs]) for r, srcs in pairs], conf, thres_view, device=device,
                      method=filter_method, pix_base=pix_base, rel_base=rel_base, voxel_size=voxel_size,
-                     voxel_reduce=voxel_reduce)
+                     voxel_reduce=voxel_reduce, outliers=outliers, normals=normals)
     os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
     masks = {k: res[k + "_mask"].cpu().numpy() for k in ("photo", "geo", "final")}
     for i, (ref_view, _) in enumerate(pairs):
         for k, m in masks.items():                                          # save_mask: bool -> uint8 * 255
             Image.fromarray(m[i].astype(np.uint8) * 255).save(os.path.join(out_folder, "mask", name(ref_view) + "_%s.png" % k))
-    vertices = res.vertices(thinned=voxel_size is not None)
-    write_ply(plyfilename, vertices)
-    return vertices
+    return write_scene_ply(plyfilename, res, thinned=voxel_size is not None)
