@@ -767,6 +767,31 @@ int mvster_cloud_knn_stats(const double* mean, long M, double std_ratio, double*
 int mvster_cloud_keep_flags(const int* cell_of_point, const int* neighbours, int nb_points, const double* mean, double* stats,
                             long M, unsigned char* flags, int* wg_counts, long* wg_offsets, void* stream);
 
+/* ---- a scan from a structure-from-motion model (csrc/geo_sfm.hip, csrc/sfm_math.h) ---- */
+
+/* q [V,V] uint64 = the quantised pair scores (units of 2^-32) over the points two views share: q[i][j] = q[j][i] = the sum of
+ * sfm::quantise(sfm::term(C_i, C_j, X_p)) over the points p both see, the diagonal 0.  centres [V,3] and points [P,3] float64;
+ * pt_ptr [P+1] int64 / pt_views [nobs] int32: per point its sorted distinct views; item_ptr [P+1] int64 = the prefix sum of
+ * L (L - 1) / 2 over the track lengths L, total = item_ptr[P] (the work items).  1 <= V <= 16384, P >= 0, total <= 2^40,
+ * theta0 in 0 .. 180, sigma1, sigma2 >= 0.05 (degrees).  What the tables hold is never used as an address unchecked: an
+ * entry out of range adds nothing.  q is zeroed here; integer atomics only, so two runs give the same bytes.  Three launches
+ * (one when total = 0). */
+int mvster_sfm_pair_scores(const double* centres, int V, const double* points, long P, const long* pt_ptr, const int* pt_views,
+                           long nobs, const long* item_ptr, long total, double theta0, double sigma1, double sigma2,
+                           unsigned long long* q, void* stream);
+
+/* Per view n [V] int32 = its distinct points with a finite depth z > 0, z = ((r20 x + r21 y) + r22 z_p) + t2 with rt [V,4]
+ * float64 = (r20, r21, r22, t2), and depth_min / depth_max [V] float64 = the z of rank n / 100 and (99 n) / 100 in ascending
+ * order (NaN for n = 0): an exact radix selection over the bit patterns, one workgroup per view, no sort.  view_ptr [V+1] int64 /
+ * view_pts [nobs] int32: per view its sorted distinct points; an entry outside 0 .. P-1 is skipped.  One launch. */
+int mvster_sfm_depth_ranges(const double* rt, int V, const double* points, long P, const long* view_ptr, const int* view_pts,
+                            long nobs, int* n, double* depth_min, double* depth_max, void* stream);
+
+/* Per row i of q [V,V]: the first num_src (1 .. 64) views j != i with q[i][j] > 0 in (q descending, j ascending) order: index
+ * [V,num_src] int32 (-1 where the list ends), value [V,num_src] uint64 (0 there), count [V] int32.  One wave per row.  One launch. */
+int mvster_sfm_select_sources(const unsigned long long* q, int V, int num_src, int* index, unsigned long long* value, int* count,
+                              void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

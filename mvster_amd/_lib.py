@@ -117,6 +117,9 @@ SIGNATURES = {
     "mvster_cloud_knn_stats_rows": [_l],
     "mvster_cloud_knn_stats": [_f, _l, ctypes.c_double, _f, _f, _f],
     "mvster_cloud_keep_flags": [_f, _f, _i, _f, _f, _l, _f, _f, _f, _f],
+    "mvster_sfm_pair_scores": [_f, _i, _f, _l, _f, _f, _l, _f, _l] + [ctypes.c_double] * 3 + [_f, _f],
+    "mvster_sfm_depth_ranges": [_f, _i, _f, _l, _f, _f, _l, _f, _f, _f, _f],
+    "mvster_sfm_select_sources": [_f, _i, _i, _f, _f, _f, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
