@@ -792,6 +792,34 @@ int mvster_sfm_depth_ranges(const double* rt, int V, const double* points, long 
 int mvster_sfm_select_sources(const unsigned long long* q, int V, int num_src, int* index, unsigned long long* value, int* count,
                               void* stream);
 
+/* ---- undistortion of a scan (csrc/geo_undistort.hip, csrc/undistort_math.h) ---- */
+
+/* cams [C,12] float64 = per camera (model id 2 SIMPLE_RADIAL / 3 RADIAL / 4 OPENCV, W, H, fx, fy, cx, cy, k1, k2, p1, p2, pad)
+ * -> out [C,8] float64 = the PINHOLE camera of its undistorted image (W', H', fx, fy, cx', cy'), the worst residual of the
+ * inversion over the 2 (W + H) border pixel centres (normalised units) and the number of border points whose residual exceeds
+ * 1e-9.  0 <= blank_pixels <= 1, 0 < min_scale <= max_scale <= 1024; scale_given != 0: the size comes from (scale_x, scale_y)
+ * and the border is not walked (residual 0).  A record that is not a camera (another model, W or H outside 1 .. 2^20, a focal
+ * length <= 0) gives zeros with residual +inf.  One workgroup per camera, min / max folds only: the bytes do not depend on the
+ * order.  One launch. */
+int mvster_undistort_cameras(const double* cams, int C, double blank_pixels, double min_scale, double max_scale, int scale_given,
+                             double scale_x, double scale_y, double* out, void* stream);
+
+/* N points xy [N,2] float64 in the pixels of their camera (camera_row [N] int32, rows of cams [C,12]) through its distortion
+ * (direction 0) or its inverse (direction 1: ten Newton steps) -> out [N,2] in the same pixel units and residual [N] (0 for
+ * direction 0; +inf where the inversion stopped, or the row is outside the table).  One lane per point.  One launch. */
+int mvster_undistort_points(const double* cams, int C, const int* camera_row, long N, int direction, const double* xy, double* out,
+                            double* residual, void* stream);
+
+/* All views of a chunk in one launch.  views [V,8] int64 = per view (source byte offset into src, destination byte offset into
+ * dst, byte offset into valid, Hs, Ws, Hd, Wd, its row in cams [C,12] and ucams [C,8] = the output of mvster_undistort_cameras);
+ * the images are uint8 [H,W,3]; dst, valid and the destination and valid offsets are multiples of 16.  group_ptr [V+1] int64 =
+ * the prefix sum of ceil(Hd Wd / 4), groups = group_ptr[V].  Every output pixel is the bilinear blend of its four source taps in
+ * fp64 rounded to a byte, or (0, 0, 0) with valid = 0 where it looks outside the source.  A view whose extents leave the
+ * buffers (src_bytes, dst_bytes, valid_bytes) writes nothing.  No atomics: two runs give the same bytes.  One launch. */
+int mvster_undistort_images(const unsigned char* src, long src_bytes, unsigned char* dst, long dst_bytes, unsigned char* valid,
+                            long valid_bytes, const long* views, const long* group_ptr, int V, long groups, const double* cams,
+                            const double* ucams, int C, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

@@ -120,6 +120,9 @@ SIGNATURES = {
     "mvster_sfm_pair_scores": [_f, _i, _f, _l, _f, _f, _l, _f, _l] + [ctypes.c_double] * 3 + [_f, _f],
     "mvster_sfm_depth_ranges": [_f, _i, _f, _l, _f, _f, _l, _f, _f, _f, _f],
     "mvster_sfm_select_sources": [_f, _i, _i, _f, _f, _f, _f],
+    "mvster_undistort_cameras": [_f, _i] + [ctypes.c_double] * 3 + [_i] + [ctypes.c_double] * 2 + [_f, _f],
+    "mvster_undistort_points": [_f, _i, _f, _l, _i, _f, _f, _f, _f],
+    "mvster_undistort_images": [_f, _l, _f, _l, _f, _l, _f, _f, _i, _l, _f, _f, _i, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

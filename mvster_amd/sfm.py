@@ -5,8 +5,15 @@ percentiles of its sparse depths -- on the GPU (csrc/geo_sfm.hip; the definition
 
 The definition is this project's own, written out in sfm_math.h; where it departs from the customary conversion scripts of the
 MVSNet family (a point seen twice in an image counts once; a partner with score zero is never listed; only finite depths
-z > 0 enter the range) DESIGN.md says so.  Undistortion is out of scope: a model with distortion raises and names COLMAP's
-``image_undistorter``.  There is no CPU fallback for the three launches."""
+z > 0 enter the range) DESIGN.md says so.  There is no CPU fallback for the three launches.
+
+Undistortion (csrc/geo_undistort.hip, the definition is csrc/undistort_math.h).  By default a model with
+distortion still raises and names COLMAP's ``image_undistorter``; ``read_sfm_model(path, distortion="keep")`` takes SIMPLE_RADIAL,
+RADIAL and OPENCV cameras as they are, ``undistorted_cameras`` gives the pinhole camera of every undistorted image,
+``undistort_points`` / ``distort_points`` take points through the inverse and the distortion, ``undistort_images`` resamples
+all images of a chunk in one launch, and ``scan_from_sfm(..., undistort=True)`` does all of it on the way to a scan.  The
+definition is this project's own, modelled on COLMAP's undistortion; COLMAP itself was not at hand to compare against, and
+DESIGN.md lists the deviations.  Fisheye, FOV, FULL_OPENCV and THIN_PRISM cameras are out of scope.  No CPU fallback either."""
 import os
 import struct
 
@@ -24,12 +31,17 @@ TWO32 = 4294967296.0
 CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3, 3), 1: ("PINHOLE", 4, 4), 2: ("SIMPLE_RADIAL", 4, 3), 3: ("RADIAL", 5, 3),
                  4: ("OPENCV", 8, 4)}
 _MODEL_IDS = {name: mid for mid, (name, _, _) in CAMERA_MODELS.items()}
+CAMERA_RECORD = 12                        # und::kCam: model id, W, H, fx, fy, cx, cy, k1, k2, p1, p2, pad
+RESIDUAL_BOUND = 1e-9                     # und::kResidualBound, normalised units
+MAX_SIDE = 1 << 20                        # und::kMaxSide
+MAX_SCALE = 1024.0
 
 
 # ---- reading a model -------------------------------------------------------------------------------------------------------------
 
-def _intrinsics(what, model, params):
-    """-> K [3,3] float64 of a camera without distortion; anything else raises."""
+def _intrinsics(what, model, params, keep=False):
+    """-> K [3,3] float64 of a camera without distortion; anything else raises.  ``keep``: distortion parameters are taken as
+    they are (finite), and K describes the distorted camera."""
     if model not in CAMERA_MODELS:
         raise RuntimeError("read_sfm_model: %s has camera model %r; only SIMPLE_PINHOLE, PINHOLE and the SIMPLE_RADIAL / RADIAL / "
                            "OPENCV models with every distortion parameter 0 are taken: run COLMAP's image_undistorter first "
@@ -37,7 +49,9 @@ def _intrinsics(what, model, params):
     name, count, first = CAMERA_MODELS[model]
     if len(params) != count:
         raise RuntimeError("read_sfm_model: %s (%s) has %d parameters, not %d" % (what, name, len(params), count))
-    if any(float(p) != 0.0 for p in params[first:]):
+    if keep and not all(np.isfinite(float(p)) for p in params):
+        raise RuntimeError("read_sfm_model: %s (%s) has a parameter that is not finite: %s" % (what, name, [float(p) for p in params]))
+    if not keep and any(float(p) != 0.0 for p in params[first:]):
         raise RuntimeError("read_sfm_model: %s (%s) has distortion parameters %s: run COLMAP's image_undistorter first and "
                            "read the undistorted model (undistortion is out of scope here)"
                            % (what, name, [float(p) for p in params[first:]]))
@@ -178,7 +192,23 @@ def structure(view_of_obs, point_of_obs, V, P):
     return dict(view_ptr=view_ptr, view_pts=pi.astype(np.int32), pt_ptr=pt_ptr, pt_views=vi[order].astype(np.int32))
 
 
-def read_sfm_model(path):
+def camera_record(model, w, h, params):
+    """A camera of ``CAMERA_MODELS`` -> its record of ``CAMERA_RECORD`` doubles (csrc/undistort_math.h): model id, W, H, fx, fy,
+    cx, cy, k1, k2, p1, p2, 0.  SIMPLE_PINHOLE and PINHOLE enter as SIMPLE_RADIAL and OPENCV with every distortion parameter 0."""
+    p = [float(x) for x in params]
+    if model in (1, 4):
+        fx, fy, cx, cy = p[:4]
+        dist = (p[4:8] if model == 4 else [0.0] * 4)
+        mid = 4
+    else:
+        fx, cx, cy = p[:3]
+        fy = fx
+        dist = [p[3], p[4] if model == 3 else 0.0, 0.0, 0.0] if model in (2, 3) else [0.0] * 4
+        mid = 3 if model == 3 else 2
+    return np.array([mid, w, h, fx, fy, cx, cy] + dist + [0.0], dtype=np.float64)
+
+
+def read_sfm_model(path, distortion="raise"):
     """``path/{cameras,images,points3D}.bin`` (preferred when both forms exist) or ``.txt`` -> dict.  Views are ordered by image
     id: ``image_ids`` [V] int64, ``names`` (list), ``camera_ids`` [V], ``qvecs`` [V,4] (w, x, y, z), ``tvecs`` [V,3], ``R``
     [V,3,3], ``centres`` [V,3] = -R^T t, ``K`` [V,3,3] at full resolution, ``sizes`` [V,2] int64 = (height, width), all float64
@@ -186,7 +216,13 @@ def read_sfm_model(path):
     view the sorted distinct points it observes and the transpose.  Observations are the POINT3D_ID column of the images
     file (the track lists of the points file are not read); an id of -1, or one the points file does not hold, is dropped.
     PINHOLE and SIMPLE_PINHOLE cameras are taken, SIMPLE_RADIAL / RADIAL / OPENCV only when every distortion parameter is 0;
-    anything else raises."""
+    anything else raises.  ``distortion="keep"``: SIMPLE_RADIAL, RADIAL and OPENCV cameras are taken with any finite
+    parameters; ``K`` and ``sizes`` then describe the distorted cameras, and the dict also holds ``camera_table`` [C,12] float64
+    (``camera_record`` of every camera a view names, by ascending camera id) and ``camera_row`` [V] int32, each view's row in
+    it: what ``undistorted_cameras`` and ``undistort_images`` take.  Any other camera model raises in both modes."""
+    if distortion not in ("raise", "keep"):
+        raise RuntimeError("read_sfm_model: distortion = %r (\"raise\" or \"keep\")" % (distortion,))
+    keep = distortion == "keep"
     def have(ext):
         return all(os.path.exists(os.path.join(path, n + ext)) for n in ("cameras", "images", "points3D"))
     if have(".bin"):
@@ -213,7 +249,7 @@ def read_sfm_model(path):
         if im[3] not in cams:
             raise RuntimeError("read_sfm_model: image %d names camera %d, which cameras does not hold" % (im[0], im[3]))
         model, w, h, params = cams[im[3]]
-        K[v] = _intrinsics("camera %d" % im[3], model, params)
+        K[v] = _intrinsics("camera %d" % im[3], model, params, keep)
         sizes[v] = (h, w)
     qvecs = np.array([im[1] for im in images], dtype=np.float64).reshape(V, 4)
     tvecs = np.array([im[2] for im in images], dtype=np.float64).reshape(V, 3)
@@ -227,6 +263,10 @@ def read_sfm_model(path):
     out = dict(image_ids=ids, names=[im[4] for im in images], camera_ids=np.array([im[3] for im in images], dtype=np.int64),
                qvecs=qvecs, tvecs=tvecs, R=R, centres=centres, K=K, sizes=sizes, point_ids=point_ids, points=points)
     out.update(structure(view_of[known], at[known], V, P))
+    if keep:
+        used = sorted(set(int(c) for c in out["camera_ids"]))
+        out["camera_table"] = np.stack([camera_record(*cams[c]) for c in used])
+        out["camera_row"] = np.searchsorted(np.array(used, dtype=np.int64), out["camera_ids"]).astype(np.int32)
     return out
 
 
@@ -436,11 +476,213 @@ def source_lists(src_index, src_q, src_count):
     return pairs, scores
 
 
+# ---- undistortion -------------------------------------------------------------------------------------------------------------------
+
+def _check_camera_table(what, camera_table):
+    """-> the table as a contiguous [C,12] float64 host array; every record must be one the kernels take"""
+    t = _host(camera_table, np.float64)
+    if t.ndim != 2 or t.shape[1] != CAMERA_RECORD or not len(t):
+        raise RuntimeError("%s: camera_table must be [C,%d] float64 with C >= 1, got %s" % (what, CAMERA_RECORD, t.shape))
+    if not np.isfinite(t).all():
+        raise RuntimeError("%s: camera_table holds a value that is not finite" % what)
+    for r, c in enumerate(t):
+        if c[0] not in (2.0, 3.0, 4.0):
+            raise RuntimeError("%s: camera row %d has model id %r; SIMPLE_RADIAL (2), RADIAL (3) and OPENCV (4) are taken" % (what, r, c[0]))
+        if c[1] != int(c[1]) or c[2] != int(c[2]) or not (1 <= c[1] <= MAX_SIDE and 1 <= c[2] <= MAX_SIDE):
+            raise RuntimeError("%s: camera row %d is %r x %r pixels (whole numbers, 1 .. %d)" % (what, r, c[1], c[2], MAX_SIDE))
+        if not (c[3] > 0 and c[4] > 0):
+            raise RuntimeError("%s: camera row %d has focal lengths %r, %r" % (what, r, c[3], c[4]))
+    return t
+
+
+def _check_rows(what, camera_row, count, C):
+    rows = _host(camera_row, np.int32)
+    if rows.shape != (count,):
+        raise RuntimeError("%s: camera_row must be [%d], got %s" % (what, count, rows.shape))
+    if count and (rows.min() < 0 or rows.max() >= C):
+        raise RuntimeError("%s: camera_row holds a row outside 0 .. %d" % (what, C - 1))
+    return rows
+
+
+def _check_scales(what, blank_pixels, min_scale, max_scale, scale):
+    blank, lo, hi = float(blank_pixels), float(min_scale), float(max_scale)
+    if not 0.0 <= blank <= 1.0:
+        raise RuntimeError("%s: blank_pixels = %r (0 .. 1)" % (what, blank_pixels))
+    if not 0.0 < lo <= hi <= MAX_SCALE:
+        raise RuntimeError("%s: min_scale = %r, max_scale = %r (0 < min_scale <= max_scale <= %g)" % (what, min_scale, max_scale, MAX_SCALE))
+    if scale is not None:
+        try:
+            sx, sy = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise RuntimeError("%s: scale = %r (None or a pair (scale_x, scale_y))" % (what, scale))
+        if not (0.0 < sx <= MAX_SCALE and 0.0 < sy <= MAX_SCALE):
+            raise RuntimeError("%s: scale = %r (both within (0, %g])" % (what, scale, MAX_SCALE))
+        scale = (sx, sy)
+    return blank, lo, hi, scale
+
+
+def _cameras_of(what, table):
+    """The kernel's [C,8] -> the dict of ``undistorted_cameras``; raises on a camera whose distortion cannot be inverted"""
+    C = len(table)
+    for r in range(C):
+        if not table[r, 6] <= RESIDUAL_BOUND:
+            raise RuntimeError("%s: camera row %d: the distortion cannot be inverted over the image: %d of its border pixels "
+                               "keep a residual above %g after the Newton steps (the worst: %g, normalised units)"
+                               % (what, r, int(table[r, 7]), RESIDUAL_BOUND, table[r, 6]))
+    K = np.zeros((C, 3, 3), np.float64)
+    K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = table[:, 2], table[:, 3], table[:, 4], table[:, 5], 1.0
+    return dict(sizes=table[:, [1, 0]].astype(np.int64), K=K, residual=table[:, 6].copy(), table=table)
+
+
+def undistorted_cameras(camera_table, blank_pixels=0.0, min_scale=0.2, max_scale=2.0, scale=None, device=None):
+    """The PINHOLE camera of every camera's undistorted image.  ``camera_table`` [C,12] float64 (``read_sfm_model(...,
+    distortion="keep")``).  The border pixel centres are undistorted (ten Newton steps each) and projected; from their extremes
+    come the per-axis scales at which no blank pixel shows (``blank_pixels=0``) or every source pixel is kept (1), clamped to
+    ``min_scale .. max_scale``; W' = max(1, int(scale_x W)), cx' = cx W' / W, the focal lengths stay.  ``scale=(sx, sy)`` sets the
+    scales and skips the border.  -> dict of host arrays after ONE read-back: ``sizes`` [C,2] int64 = (height, width), ``K``
+    [C,3,3], ``residual`` [C] (the worst over the border, normalised units) and ``table`` [C,8], what ``undistort_images``
+    takes.  Raises when a residual exceeds 1e-9: that camera's distortion cannot be inverted over its image."""
+    what = "undistorted_cameras"
+    blank, lo, hi, scale = _check_scales(what, blank_pixels, min_scale, max_scale, scale)
+    table = _check_camera_table(what, camera_table)
+    dev = _device(what, device)
+    with torch.cuda.device(dev):
+        cams = torch.from_numpy(table).to(dev)
+        out = torch.empty(len(table), 8, device=dev, dtype=torch.float64)
+        sx, sy = scale if scale is not None else (1.0, 1.0)
+        _lib.check(_lib.load().mvster_undistort_cameras(cams.data_ptr(), len(table), blank, lo, hi, int(scale is not None), sx, sy,
+                                                        out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "undistort_cameras")
+        got = out.cpu().numpy()                                                 # the one read-back
+    return _cameras_of(what, got)
+
+
+def _points(what, direction, camera_table, camera_row, xy, device):
+    table = _check_camera_table(what, camera_table)
+    if not torch.is_tensor(xy):
+        xy = torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64))
+    if xy.dtype != torch.float64 or xy.ndim != 2 or xy.shape[1] != 2:
+        raise RuntimeError("%s: xy must be [N,2] float64, got %s %s" % (what, tuple(xy.shape), xy.dtype))
+    N = xy.shape[0]
+    rows = _check_rows(what, camera_row, N, len(table))
+    dev = _device(what, device)
+    with torch.cuda.device(dev):
+        xy = xy.to(dev).contiguous()
+        out = torch.empty(N, 2, device=dev, dtype=torch.float64)
+        residual = torch.empty(N, device=dev, dtype=torch.float64)
+        if N:
+            cams, rows_d = torch.from_numpy(table).to(dev), torch.from_numpy(rows).to(dev)
+            _lib.check(_lib.load().mvster_undistort_points(cams.data_ptr(), len(table), rows_d.data_ptr(), N, direction, xy.data_ptr(),
+                                                           out.data_ptr(), residual.data_ptr(),
+                                                           torch.cuda.current_stream(dev).cuda_stream), "undistort_points")
+    return out, residual
+
+
+def undistort_points(camera_table, camera_row, xy, device=None):
+    """``xy`` [N,2] float64 (array or tensor), pixel coordinates in the distorted images of the cameras ``camera_row`` [N] names
+    -> (``xy'`` [N,2], ``residual`` [N]) float64 on the GPU: the points without the distortion, in the pixels of the SAME fx,
+    fy, cx, cy (apply an undistorted camera's cx' - cx yourself), and what the ten Newton steps left (normalised units; +inf
+    where they stopped: a determinant <= 0 or an iterate that is not finite).  No read-back."""
+    return _points("undistort_points", 1, camera_table, camera_row, xy, device)
+
+
+def distort_points(camera_table, camera_row, xy, device=None):
+    """The other direction of ``undistort_points`` -> ``xy'`` [N,2] float64 on the GPU.  No read-back."""
+    return _points("distort_points", 0, camera_table, camera_row, xy, device)[0]
+
+
+def _round16(n):
+    return (int(n) + 15) // 16 * 16
+
+
+def undistort_images(images, camera_table, camera_row, cameras=None, chunk_bytes=1 << 30, keep_on_device=False, device=None):
+    """``images``: a list of uint8 [H,W,3] arrays or tensors (host or GPU), image k taken by camera ``camera_row[k]`` of
+    ``camera_table`` -> (``images'``, ``valid``, ``cameras``): the undistorted images (uint8 [H',W',3]), per image a uint8 [H',W']
+    mask (0 where the pixel looks outside the source; such a pixel is black), and the dict of ``undistorted_cameras`` (made
+    with its defaults when ``cameras`` is None).  The list is worked through in chunks of at most ``chunk_bytes`` of source
+    (an image larger than that is a chunk of its own): one upload, ONE launch and one read-back per chunk.
+    ``keep_on_device=True`` returns GPU tensors and reads nothing back.  An image whose size differs from its camera's raises."""
+    what = "undistort_images"
+    if int(chunk_bytes) != chunk_bytes or int(chunk_bytes) < 1:
+        raise RuntimeError("%s: chunk_bytes = %r (a whole number of bytes, at least 1)" % (what, chunk_bytes))
+    table = _check_camera_table(what, camera_table)
+    images = list(images)
+    rows = _check_rows(what, camera_row, len(images), len(table))
+    for k, img in enumerate(images):
+        if not torch.is_tensor(img):
+            images[k] = img = np.asarray(img)
+        dtype_ok = img.dtype == (torch.uint8 if torch.is_tensor(img) else np.uint8)
+        if not dtype_ok or img.ndim != 3 or img.shape[2] != 3:
+            raise RuntimeError("%s: image %d must be uint8 [H,W,3], got %s %s" % (what, k, tuple(img.shape), img.dtype))
+        H, W = int(table[rows[k], 2]), int(table[rows[k], 1])
+        if tuple(img.shape[:2]) != (H, W):
+            raise RuntimeError("%s: image %d is %dx%d but its camera (row %d) says %dx%d"
+                               % (what, k, img.shape[0], img.shape[1], rows[k], H, W))
+    if cameras is not None:
+        ucam = _host(cameras["table"], np.float64)
+        if ucam.shape != (len(table), 8):
+            raise RuntimeError("%s: cameras[\"table\"] must be [%d,8], got %s" % (what, len(table), ucam.shape))
+        cameras = _cameras_of(what, ucam)
+    dev = _device(what, device)
+    if cameras is None:
+        cameras = undistorted_cameras(table, device=dev)
+    ucam = np.ascontiguousarray(cameras["table"], dtype=np.float64)
+    chunks, start, used = [], 0, 0
+    for k, img in enumerate(images):                                             # chunks of at most chunk_bytes of source
+        n = 3 * img.shape[0] * img.shape[1]
+        if k > start and used + n > int(chunk_bytes):
+            chunks.append((start, k))
+            start, used = k, 0
+        used += n
+    if images:
+        chunks.append((start, len(images)))
+    out_images, out_valid = [], []
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cams_d, ucam_d = torch.from_numpy(table).to(dev), torch.from_numpy(ucam).to(dev)
+        for lo, hi in chunks:
+            V = hi - lo
+            views, group_ptr = np.zeros((V, 8), np.int64), np.zeros(V + 1, np.int64)
+            order = [k for k in range(lo, hi) if not torch.is_tensor(images[k])] + [k for k in range(lo, hi) if torch.is_tensor(images[k])]
+            src_at, dst_at, valid_at = 0, 0, 0
+            for k in order:                                                    # host images first: they go up in one copy
+                Hs, Ws = images[k].shape[:2]
+                Hd, Wd = (int(s) for s in cameras["sizes"][rows[k]])
+                views[k - lo] = (src_at, dst_at, valid_at, Hs, Ws, Hd, Wd, rows[k])
+                src_at, dst_at, valid_at = src_at + 3 * Hs * Ws, dst_at + _round16(3 * Hd * Wd), valid_at + _round16(Hd * Wd)
+            group_ptr[1:] = np.cumsum((views[:, 5] * views[:, 6] + 3) // 4)
+            src = torch.empty(src_at, device=dev, dtype=torch.uint8)
+            host = [images[k].reshape(-1) for k in order if not torch.is_tensor(images[k])]
+            if host:
+                block = torch.from_numpy(np.concatenate(host) if len(host) > 1 else np.ascontiguousarray(host[0]))
+                src[:block.numel()].copy_(block)                                # the one upload
+            for k in order:
+                if torch.is_tensor(images[k]):
+                    at = int(views[k - lo, 0])
+                    src[at:at + images[k].numel()].copy_(images[k].reshape(-1))
+            out = torch.empty(dst_at + valid_at, device=dev, dtype=torch.uint8)   # images, then masks: one buffer, one read-back
+            tables = torch.from_numpy(np.concatenate([views.reshape(-1), group_ptr])).to(dev)
+            _lib.check(lib.mvster_undistort_images(src.data_ptr(), src_at, out.data_ptr(), dst_at, out.data_ptr() + dst_at, valid_at,
+                                                   tables.data_ptr(), tables.data_ptr() + views.size * 8, V, int(group_ptr[-1]),
+                                                   cams_d.data_ptr(), ucam_d.data_ptr(), len(table), stream), "undistort_images")
+            got = out if keep_on_device else out.cpu().numpy()                  # (the chunk's one read-back)
+            for k in range(lo, hi):
+                _, d, m, _, _, Hd, Wd, _ = (int(x) for x in views[k - lo])
+                img, mask = got[d:d + 3 * Hd * Wd], got[dst_at + m:dst_at + m + Hd * Wd]
+                out_images.append(img.view(Hd, Wd, 3) if keep_on_device else img.reshape(Hd, Wd, 3).copy())
+                out_valid.append(mask.view(Hd, Wd) if keep_on_device else mask.reshape(Hd, Wd).copy())
+    return out_images, out_valid, cameras
+
+
 # ---- to a scan ------------------------------------------------------------------------------------------------------------------------
 
-def assemble_scan(model, graph, load_image):
+def assemble_scan(model, graph, load_image, K=None, transform=None):
     """A model (``read_sfm_model``), its ``view_graph`` and ``load_image(view) -> uint8 [H,W,3]`` -> the scan dict of
-    ``scan_from_sfm``.  Host work only."""
+    ``scan_from_sfm``.  Host work only, unless ``transform`` does more.  ``K`` [V,3,3]: the views' full-resolution intrinsics in
+    place of the model's; ``transform(images, kept views) -> (images, dict of further entries)`` is applied to the loaded
+    (and size-checked) images of the kept views: how ``scan_from_sfm(..., undistort=True)`` puts undistorted images, their
+    cameras and their ``valid`` masks into the scan."""
     keep = np.nonzero(graph["n_obs"] > 0)[0]
     if not len(keep):
         raise RuntimeError("scan_from_sfm: no view of the model has a sparse point in front of it")
@@ -462,14 +704,19 @@ def assemble_scan(model, graph, load_image):
         if kept:
             pairs.append((slot[v], [j for j, _ in kept]))
             scores.append([s for _, s in kept])
-    return dict(images=images, Ks=formats._quarter(model["K"][keep].astype(np.float32)), Es=Es,
+    more = {}
+    if transform is not None:
+        images, more = transform(images, keep)
+    Kfull = model["K"] if K is None else np.asarray(K, dtype=np.float64)
+    return dict(more, images=images, Ks=formats._quarter(Kfull[keep].astype(np.float32)), Es=Es,
                 depth_ranges=[(float(graph["depth_min"][v]), float(graph["depth_max"][v])) for v in keep], pairs=pairs,
                 pair_scores=scores, view_ids=[int(model["image_ids"][v]) for v in keep],
                 names=[model["names"][v] for v in keep],
                 dropped_views=[int(model["image_ids"][v]) for v in np.nonzero(graph["n_obs"] <= 0)[0]])
 
 
-def scan_from_sfm(model_dir, image_dir, theta0=5.0, sigma1=1.0, sigma2=10.0, num_src=10, device=None):
+def scan_from_sfm(model_dir, image_dir, theta0=5.0, sigma1=1.0, sigma2=10.0, num_src=10, device=None, undistort=False,
+                  blank_pixels=0.0, keep_on_device=False):
     """A COLMAP sparse model and its (undistorted) images -> the dict ``scan.read_scan_folder`` returns: ``images`` (list of
     uint8 [H,W,3], ``image_dir/<name>``), ``Ks`` [V,3,3] float32 in the quarter-resolution convention (rows 0-1 divided by 4),
     ``Es`` [V,4,4] float32, ``depth_ranges`` = [(depth_min, depth_max)] for ``depth_range_kind="min_max"``, ``pairs`` (indices
@@ -477,12 +724,31 @@ def scan_from_sfm(model_dir, image_dir, theta0=5.0, sigma1=1.0, sigma2=10.0, num
     views without a single sparse point in front of them, which have no depth range and are left out (of the lists of the
     others too, which are not filled up again).  A view may have fewer than ``num_src`` sources: run ``infer_scan`` /
     ``reconstruct_scan`` with ``short_sources="fewer_views"``, ``depth_range_kind="min_max"`` and ``max_h=`` / ``max_w=`` or
-    ``img_wh=``."""
+    ``img_wh=``.
+
+    ``undistort=True``: the model is read with ``distortion="keep"`` and ``image_dir`` holds the photographs the model was made
+    from.  The view graph is the same (it depends on the poses and the sparse points only); the images of the kept views are
+    undistorted on the GPU (``undistort_images``, ``blank_pixels`` as in ``undistorted_cameras``), ``Ks`` are the undistorted
+    cameras' and ``valid`` lists a uint8 [H',W'] mask per view.  ``keep_on_device=True`` leaves images and masks on the GPU, as
+    ``infer_scan`` takes them.  A model without distortion goes the same way: its cameras are then rescaled by the border rule
+    (ideally scale 1, but a size may lose a pixel to rounding), and the images are resampled once."""
     from PIL import Image
-    model = read_sfm_model(model_dir)
+    if not undistort and (blank_pixels != 0.0 or keep_on_device):
+        raise RuntimeError("scan_from_sfm: blank_pixels and keep_on_device belong to undistort=True")
+    if undistort:
+        _check_scales("scan_from_sfm", blank_pixels, 0.2, 2.0, None)
+    model = read_sfm_model(model_dir, distortion="keep" if undistort else "raise")
+    load = lambda v: np.array(Image.open(os.path.join(image_dir, model["names"][v])).convert("RGB"), dtype=np.uint8)
     graph = view_graph(model, theta0, sigma1, sigma2, num_src, device)
-    return assemble_scan(model, graph, lambda v: np.array(Image.open(os.path.join(image_dir, model["names"][v])).convert("RGB"),
-                                                          dtype=np.uint8))
+    if not undistort:
+        return assemble_scan(model, graph, load)
+    cams = undistorted_cameras(model["camera_table"], blank_pixels, device=device)
+
+    def transform(images, keep):
+        out, valid, _ = undistort_images(images, model["camera_table"], model["camera_row"][keep], cameras=cams,
+                                         keep_on_device=keep_on_device, device=device)
+        return out, dict(valid=valid)
+    return assemble_scan(model, graph, load, K=cams["K"][model["camera_row"]], transform=transform)
 
 
 def write_scan_folder(scan, root, ndepths=192):
@@ -507,7 +773,7 @@ def write_scan_folder(scan, root, ndepths=192):
         os.makedirs(os.path.join(root, sub), exist_ok=True)
     for v in range(V):
         name = "{:0>8}".format(ids[v])
-        Image.fromarray(np.asarray(scan["images"][v], dtype=np.uint8)).save(os.path.join(root, "images", name + ".jpg"))
+        Image.fromarray(_host(scan["images"][v], np.uint8)).save(os.path.join(root, "images", name + ".jpg"))
         K = Ks[v].copy()
         K[:2, :] *= 4.0                                                         # exact: back to full resolution
         lo, hi = float(scan["depth_ranges"][v][0]), float(scan["depth_ranges"][v][1])
