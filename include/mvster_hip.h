@@ -820,6 +820,46 @@ int mvster_undistort_images(const unsigned char* src, long src_bytes, unsigned c
                             long valid_bytes, const long* views, const long* group_ptr, int V, long groups, const double* cams,
                             const double* ucams, int C, void* stream);
 
+/* ---- meshing a scan: TSDF integration and marching tetrahedra (csrc/geo_mesh.hip, csrc/tsdf_math.h) ---- */
+
+/* Tiles of 256 nodes of a grid of `nodes` nodes: the length of vcounts / tcounts; voffsets / toffsets hold one more.
+ * MVSTER_ERR_SHAPE for nodes outside 8 .. 2^31 - 1. */
+int mvster_mesh_blocks(long nodes);
+
+/* All V views of a scan fused into the grid of nx x ny x nz nodes (each >= 2, at most 2^31 - 1 in all; node (i, j, k) at
+ * origin + voxel (i, j, k), index i + nx (j + ny k)) in ONE launch: depth [V,H,W] float32, mask [V,H,W] uint8 (0 = not used),
+ * images [V,H,W,3] uint8, views [V,21] float64 = K (9, row major; third row taken as 0 0 1), R (9), t (3), all on the device.
+ * Per node, over the views in view order (csrc/tsdf_math.h has every step): the nearest pixel of its projection, the projective
+ * distance sdf = d - c_z, dropped below -trunc, f = min(1, sdf / trunc) -> tsdf [n] float32 = the mean of f (1 where no view
+ * counted), weight [n] int32 = the views counted, rgb [n,3] uint8 = the rounded mean of the pixels with sdf <= trunc,
+ * has_color [n] uint8.  fp64, no atomics: two runs give the same bytes.  MVSTER_ERR_SHAPE before any launch for a bad grid, V, H
+ * or W < 1, H or W above 2^20, a voxel or trunc that is not a positive finite number. */
+int mvster_tsdf_integrate(const float* depth, const unsigned char* mask, const unsigned char* images, const double* views, int V,
+                          int H, int W, double ox, double oy, double oz, double voxel, int nx, int ny, int nz, double trunc,
+                          float* tsdf, int* weight, unsigned char* rgb, unsigned char* has_color, void* stream);
+
+/* The counting passes of an extraction (a node is known iff weight >= min_weight, inside iff tsdf < 0; csrc/tsdf_math.h):
+ * edge_mask [n] uint8 = bit d (1 .. 7) set where the edge from node n to the node at offset d (bits x, y, z) carries a vertex,
+ * rank [n] uint16 = the vertices of the nodes before n in its tile, vcounts / tcounts [tiles] int32 (scratch), voffsets /
+ * toffsets [tiles + 1] int64 = the exclusive scans of the vertices and the triangles per tile; their last words are the two
+ * counts, the caller's one read-back.  Four launches, no atomics. */
+int mvster_mesh_count(const float* tsdf, const int* weight, int nx, int ny, int nz, int min_weight, unsigned char* edge_mask,
+                      unsigned short* rank, int* vcounts, int* tcounts, long* voffsets, long* toffsets, void* stream);
+
+/* vertices [Nv,3] float32 and colors [Nv,3] uint8 in the order owner node, then d, with edge_mask / rank / voffsets as
+ * mvster_mesh_count left them and Nv the count read back.  Nv = 0 launches nothing; Nv above 2^31 - 1 (the triangles hold int32
+ * indices) is MVSTER_ERR_SHAPE and launches nothing.  One launch. */
+int mvster_mesh_emit_vertices(const float* tsdf, const unsigned char* rgb, const unsigned char* has_color, double ox, double oy,
+                              double oz, double voxel, int nx, int ny, int nz, const unsigned char* edge_mask,
+                              const unsigned short* rank, const long* voffsets, long Nv, float* vertices, unsigned char* colors,
+                              void* stream);
+
+/* triangles [Nt,3] int32 (vertex numbers, counter-clockwise seen from the tsdf > 0 side) in the order cell, tetrahedron,
+ * triangle.  Nt = 0 launches nothing; Nv above 2^31 - 1 is MVSTER_ERR_SHAPE.  One launch. */
+int mvster_mesh_emit_triangles(const float* tsdf, const int* weight, int nx, int ny, int nz, int min_weight,
+                               const unsigned char* edge_mask, const unsigned short* rank, const long* voffsets,
+                               const long* toffsets, long Nv, long Nt, int* triangles, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

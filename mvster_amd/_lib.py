@@ -123,6 +123,11 @@ SIGNATURES = {
     "mvster_undistort_cameras": [_f, _i] + [ctypes.c_double] * 3 + [_i] + [ctypes.c_double] * 2 + [_f, _f],
     "mvster_undistort_points": [_f, _i, _f, _l, _i, _f, _f, _f, _f],
     "mvster_undistort_images": [_f, _l, _f, _l, _f, _l, _f, _f, _i, _l, _f, _f, _i, _f],
+    "mvster_mesh_blocks": [_l],
+    "mvster_tsdf_integrate": [_f, _f, _f, _f, _i, _i, _i] + [ctypes.c_double] * 4 + [_i, _i, _i, ctypes.c_double, _f, _f, _f, _f, _f],
+    "mvster_mesh_count": [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f],
+    "mvster_mesh_emit_vertices": [_f, _f, _f] + [ctypes.c_double] * 4 + [_i, _i, _i, _f, _f, _f, _l, _f, _f, _f],
+    "mvster_mesh_emit_triangles": [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _l, _l, _f, _f],
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

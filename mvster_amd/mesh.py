@@ -1,0 +1,452 @@
+"""Meshing a scan on the GPU: the filtered depth maps of a scan fused into a truncated signed distance
+field (TSDF) on a dense grid, and the welded, indexed, coloured triangle mesh of its zero level by marching tetrahedra.
+
+The definition is ``mvster_amd/csrc/tsdf_math.h``; the kernels are ``mvster_amd/csrc/geo_mesh.hip``.  ``integrate_tsdf`` is one
+launch for all views of a scan, ``extract_mesh`` is count -> scan -> emit with one read-back (the two counts), no atomics: two
+runs give the same bytes, and the bytes are those of the host build of the header (tests/test_gpu_mesh.py).  It is this
+project's own definition, modelled on KinectFusion / Open3D-style integration: nearest-pixel sampling, the projective distance
+along z, unit weights, a dense grid.  Open3D is not at hand, so agreement with it is untested.  There is no CPU fallback.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_NODES = (1 << 31) - 1               # tsdf::kMaxNodes: node and vertex numbers are int32
+MAX_SIDE = 1 << 20                      # H, W at most
+NODE_BYTES = 12 + 3                     # tsdf, weight, rgb, has_color of the volume + edge mask and rank of an extraction
+MEMORY_BUDGET = 8 << 30                 # bytes a mesh_scene volume and its extraction may take
+MIN_TRUNC_VOXELS = 2.0                  # trunc >= 2 voxels: the ends of a crossing edge (length <= sqrt(3) voxels) are not both clamped
+DEFAULT_TRUNC_VOXELS = 4.0
+
+TSDFMesh = collections.namedtuple("TSDFMesh", "voxel_size trunc min_weight", defaults=(None, 2))
+Mesh = collections.namedtuple("Mesh", "vertices colors triangles")
+
+
+class TSDFVolume:
+    """What ``integrate_tsdf`` returns: ``tsdf`` [nz,ny,nx] float32, ``weight`` [nz,ny,nx] int32 (the views counted), ``rgb``
+    [nz,ny,nx,3] uint8 and ``has_color`` [nz,ny,nx] uint8 on the GPU, and the grid: ``origin`` (3 floats), ``voxel_size``,
+    ``dims`` = (nx, ny, nz), ``trunc``.  Node (i, j, k) is at origin + voxel_size * (i, j, k) and at [k, j, i] in the tensors."""
+
+    def __init__(self, tsdf, weight, rgb, has_color, origin, voxel_size, dims, trunc):
+        self.tsdf, self.weight, self.rgb, self.has_color = tsdf, weight, rgb, has_color
+        self.origin, self.voxel_size, self.dims, self.trunc = tuple(float(o) for o in origin), float(voxel_size), tuple(dims), trunc
+
+    def params(self):
+        return dict(origin=self.origin, voxel_size=self.voxel_size, dims=self.dims, trunc=self.trunc)
+
+
+# ---- argument checks (all on the host, before any device call) ----------------------------------------------------------------------
+
+def _number(what, name, value, positive=True):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: %s must be a number, not %r" % (what, name, value)) from None
+    if not math.isfinite(v) or (positive and not v > 0):
+        raise RuntimeError("%s: %s must be finite%s, not %r" % (what, name, " and > 0" if positive else "", value))
+    return v
+
+
+def _check_trunc(what, voxel, trunc):
+    """-> trunc, ``DEFAULT_TRUNC_VOXELS`` voxels where it is None; refused below ``MIN_TRUNC_VOXELS`` voxels."""
+    if trunc is None:
+        return DEFAULT_TRUNC_VOXELS * voxel
+    t = _number(what, "trunc", trunc)
+    if t < MIN_TRUNC_VOXELS * voxel:
+        raise RuntimeError("%s: trunc must be >= %g * voxel_size = %r, not %r (both ends of a crossing edge could be clamped)" %
+                           (what, MIN_TRUNC_VOXELS, MIN_TRUNC_VOXELS * voxel, trunc))
+    return t
+
+
+def _check_min_weight(what, min_weight):
+    if isinstance(min_weight, bool) or not isinstance(min_weight, (int, np.integer)) or not 1 <= int(min_weight) < (1 << 31):
+        raise RuntimeError("%s: min_weight must be an integer >= 1, not %r" % (what, min_weight))
+    return int(min_weight)
+
+
+def _check_dims(what, dims):
+    try:
+        d = tuple(int(x) for x in dims)
+        exact = all(int(x) == x for x in dims)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: dims must be three integers (nx, ny, nz), not %r" % (what, dims)) from None
+    if len(d) != 3 or not exact:
+        raise RuntimeError("%s: dims must be three integers (nx, ny, nz), not %r" % (what, dims))
+    if min(d) < 2:
+        raise RuntimeError("%s: a grid needs at least 2 nodes per axis, not %r" % (what, d))
+    if d[0] * d[1] * d[2] > MAX_NODES:
+        raise RuntimeError("%s: a grid holds at most 2^31 - 1 nodes, not %d (%r)" % (what, d[0] * d[1] * d[2], d))
+    return d
+
+
+def _check_origin(what, origin):
+    try:
+        o = tuple(float(x) for x in origin)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: origin must be three numbers, not %r" % (what, origin)) from None
+    if len(o) != 3 or not all(math.isfinite(x) for x in o):
+        raise RuntimeError("%s: origin must be three finite numbers, not %r" % (what, origin))
+    return o
+
+
+def check_mesh_spec(what, mesh):
+    """The ``mesh`` keyword of the scan-level entry points, checked before anything runs -> (voxel, trunc, min_weight) or None."""
+    if mesh is None:
+        return None
+    if not isinstance(mesh, TSDFMesh):
+        raise RuntimeError("%s: mesh must be None or a TSDFMesh, not %r" % (what, mesh))
+    voxel = _number(what, "mesh.voxel_size", mesh.voxel_size)
+    return voxel, _check_trunc(what, voxel, mesh.trunc), _check_min_weight(what, mesh.min_weight)
+
+
+def _shape(x):
+    if isinstance(x, (torch.Tensor, np.ndarray)):
+        return tuple(x.shape)
+    x = list(x)
+    shapes = {tuple(m.shape) for m in x}
+    if len(shapes) != 1:
+        raise RuntimeError("maps of different sizes inside one scan: %s" % sorted(shapes))
+    return (len(x),) + shapes.pop()
+
+
+def _stack(x, dev, dtype):
+    """Maps of a scan (array, tensor, or a sequence of either) -> one contiguous tensor [V, ...] of ``dtype`` on ``dev``."""
+    if not isinstance(x, (torch.Tensor, np.ndarray)):
+        x = list(x)
+        if all(isinstance(m, torch.Tensor) for m in x):
+            x = torch.stack([m.to(dev) for m in x])
+        else:
+            x = np.stack([m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in x])
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    return x.to(dev, dtype).contiguous()
+
+
+def _cameras(what, Ks, Es, V):
+    """-> views [V,21] float64: K (row major), R, t.  K's third row must be 0 0 1 (the kernels do not read it)."""
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+    Ks, Es = [host(k) for k in Ks], [host(e) for e in Es]
+    if len(Ks) != V or len(Es) != V:
+        raise RuntimeError("%s: %d depth maps for %d intrinsics and %d extrinsics" % (what, V, len(Ks), len(Es)))
+    rows = np.empty((V, 21), np.float64)
+    for v, (K, E) in enumerate(zip(Ks, Es)):
+        if K.shape != (3, 3) or E.shape != (4, 4):
+            raise RuntimeError("%s: Ks[%d] must be [3,3] and Es[%d] [4,4], not %s and %s" % (what, v, v, K.shape, E.shape))
+        if not (np.isfinite(K).all() and np.isfinite(E).all()):
+            raise RuntimeError("%s: the camera of view %d holds a value that is not finite" % (what, v))
+        if tuple(K[2]) != (0.0, 0.0, 1.0):
+            raise RuntimeError("%s: the third row of Ks[%d] must be 0 0 1, not %r" % (what, v, tuple(K[2])))
+        rows[v, :9], rows[v, 9:18], rows[v, 18:] = K.reshape(-1), E[:3, :3].reshape(-1), E[:3, 3]
+    return rows
+
+
+def _device(what, device, tensors):
+    if device is None:
+        devs = [m.device for x in tensors for m in ([x] if isinstance(x, torch.Tensor) else
+                                                    x if not isinstance(x, np.ndarray) and x is not None else [])
+                if isinstance(m, torch.Tensor) and m.is_cuda]
+        if not devs:
+            raise RuntimeError("mvster_amd.mesh.%s runs on MI355X only: pass device= or tensors on the GPU (there is no CPU "
+                               "fallback)" % what)
+        device = devs[0]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("mvster_amd.mesh.%s runs on MI355X only (there is no CPU fallback)" % what)
+    return dev
+
+
+def _check_maps(what, depths, masks, images):
+    ds = _shape(depths)
+    if len(ds) != 3 or ds[0] < 1 or ds[1] < 1 or ds[2] < 1 or max(ds[1:]) > MAX_SIDE:
+        raise RuntimeError("%s: depths must be [V,H,W] with V, H, W >= 1 and H, W <= 2^20, not %s" % (what, ds))
+    if masks is not None and _shape(masks) != ds:
+        raise RuntimeError("%s: masks must have the shape of depths %s, not %s" % (what, ds, _shape(masks)))
+    if _shape(images) != ds + (3,):
+        raise RuntimeError("%s: images must be [V,H,W,3] with the V, H, W of depths %s, not %s" % (what, ds, _shape(images)))
+    first = images if isinstance(images, (torch.Tensor, np.ndarray)) else list(images)[0]
+    if first.dtype not in (torch.uint8, np.dtype(np.uint8)):
+        raise RuntimeError("%s: images must be uint8, not %s" % (what, first.dtype))
+    return ds
+
+
+# ---- integration ------------------------------------------------------------------------------------------------------------------------
+
+def integrate_tsdf(depths, masks, images, Ks, Es, origin, voxel_size, dims, trunc, device=None, fill=None):
+    """All views of a scan fused into a TSDF on the GPU in one launch (``mvster_tsdf_integrate``).  ``depths`` [V,H,W]
+    (converted to float32), ``masks`` [V,H,W] (a pixel is used where its mask is not 0; None: every pixel), ``images``
+    [V,H,W,3] uint8, ``Ks`` [V,3,3] (third row 0 0 1) and ``Es`` [V,4,4] world -> camera, widened to float64: arrays,
+    tensors or sequences of them.  The grid has ``dims`` = (nx, ny, nz) nodes (each >= 2, at most 2^31 - 1 in all), node
+    (i, j, k) at ``origin`` + ``voxel_size`` (i, j, k) in float64.  Per node and view: the nearest pixel of the node's
+    projection; depth d there (skipped where masked, not finite or <= 0); sdf = d - z of the node in the camera; skipped
+    where sdf < -``trunc``; f = min(1, sdf / trunc).  -> ``TSDFVolume``: tsdf = the mean of f over the views counted (1 where
+    none), weight = their number, rgb = the rounded mean of the pixels with sdf <= trunc.  Every view has weight 1
+    (per-pixel confidence weights are out of scope).  Nothing is read back.  ``fill`` (tests): a byte the outputs are filled with
+    before the kernel writes them.  No CPU fallback."""
+    what = "integrate_tsdf"
+    V, H, W = _check_maps(what, depths, masks, images)
+    views = _cameras(what, Ks, Es, V)
+    o = _check_origin(what, origin)
+    voxel = _number(what, "voxel_size", voxel_size)
+    nx, ny, nz = _check_dims(what, dims)
+    t = _number(what, "trunc", trunc)
+    dev = _device(what, device, (depths, masks, images))
+    depth = _stack(depths, dev, torch.float32)
+    mask = torch.ones(V, H, W, device=dev, dtype=torch.uint8) if masks is None else (_stack(masks, dev, torch.bool)).to(torch.uint8)
+    img = _stack(images, dev, torch.uint8)
+    vol = TSDFVolume(torch.empty(nz, ny, nx, device=dev, dtype=torch.float32), torch.empty(nz, ny, nx, device=dev, dtype=torch.int32),
+                     torch.empty(nz, ny, nx, 3, device=dev, dtype=torch.uint8), torch.empty(nz, ny, nx, device=dev, dtype=torch.uint8),
+                     o, voxel, (nx, ny, nz), t)
+    if fill is not None:
+        for out in (vol.tsdf, vol.weight, vol.rgb, vol.has_color):
+            out.view(torch.uint8).fill_(int(fill))
+    with torch.cuda.device(dev):
+        table = torch.from_numpy(views).to(dev)
+        rc = _lib.load().mvster_tsdf_integrate(depth.data_ptr(), mask.data_ptr(), img.data_ptr(), table.data_ptr(), V, H, W, o[0], o[1],
+                                               o[2], voxel, nx, ny, nz, t, vol.tsdf.data_ptr(), vol.weight.data_ptr(),
+                                               vol.rgb.data_ptr(), vol.has_color.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "tsdf_integrate")
+    return vol
+
+
+# ---- extraction --------------------------------------------------------------------------------------------------------------------------
+
+def _check_volume(what, volume):
+    if not isinstance(volume, TSDFVolume):
+        raise RuntimeError("%s: volume must be a TSDFVolume, not %s" % (what, type(volume).__name__))
+    nx, ny, nz = _check_dims(what, volume.dims)
+    _check_origin(what, volume.origin)
+    _number(what, "volume.voxel_size", volume.voxel_size)
+    for name, shape, dtype in (("tsdf", (nz, ny, nx), torch.float32), ("weight", (nz, ny, nx), torch.int32),
+                               ("rgb", (nz, ny, nx, 3), torch.uint8), ("has_color", (nz, ny, nx), torch.uint8)):
+        t = getattr(volume, name)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype:
+            raise RuntimeError("%s: volume.%s must be a %s tensor of shape %s" % (what, name, dtype, shape))
+    for name in ("tsdf", "weight", "rgb", "has_color"):
+        t = getattr(volume, name)
+        if not t.is_cuda or t.device != volume.tsdf.device:
+            raise RuntimeError("%s: volume.%s must be on the GPU of volume.tsdf (there is no CPU fallback)" % (what, name))
+    return nx, ny, nz
+
+
+def extract_mesh(volume, min_weight=1, fill=None):
+    """The zero level of a ``TSDFVolume`` as a welded, indexed, coloured triangle mesh by marching tetrahedra on the GPU
+    (``mvster_mesh_count`` / ``mvster_mesh_emit_vertices`` / ``mvster_mesh_emit_triangles``; defined exactly in
+    mvster_amd/csrc/tsdf_math.h).  A node is known where weight >= ``min_weight`` and inside where tsdf < 0; a cell takes part
+    where its 8 corners are known.  -> ``Mesh``: ``vertices`` [Nv,3] float32, ``colors`` [Nv,3] uint8, ``triangles`` [Nt,3]
+    int32, on the GPU; vertices in the order of their owner node and edge, triangles in the order cell, tetrahedron, triangle,
+    counter-clockwise seen from the free-space (tsdf > 0) side; every vertex is used, none appears twice.  A node with
+    tsdf == 0 is outside, so a vertex may coincide with a node and triangles without area are kept.  Nv = Nt = 0 is a valid
+    result.  One read-back (the two counts).  ``fill`` (tests): a byte the outputs are filled with before the kernels write
+    them.  No CPU fallback."""
+    what = "extract_mesh"
+    mw = _check_min_weight(what, min_weight)
+    nx, ny, nz = _check_volume(what, volume)
+    dev = volume.tsdf.device
+    tsdf, weight, rgb, has = (getattr(volume, k).contiguous() for k in ("tsdf", "weight", "rgb", "has_color"))
+    lib = _lib.load()
+    nodes = nx * ny * nz
+    tiles = lib.mvster_mesh_blocks(nodes)
+    _lib.check(min(tiles, 0), "mesh_blocks")
+    o, voxel = volume.origin, volume.voxel_size
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        edge_mask = torch.empty(nodes, device=dev, dtype=torch.uint8)
+        rank = torch.empty(nodes, device=dev, dtype=torch.int16)
+        counts = torch.empty(2, tiles, device=dev, dtype=torch.int32)
+        offsets = torch.empty(2, tiles + 1, device=dev, dtype=torch.int64)
+        _lib.check(lib.mvster_mesh_count(tsdf.data_ptr(), weight.data_ptr(), nx, ny, nz, mw, edge_mask.data_ptr(), rank.data_ptr(),
+                                         counts[0].data_ptr(), counts[1].data_ptr(), offsets[0].data_ptr(), offsets[1].data_ptr(),
+                                         stream), "mesh_count")
+        nv, nt = (int(c) for c in offsets[:, tiles].cpu())                        # the one read-back
+        if nv > MAX_NODES:
+            raise RuntimeError("extract_mesh: the mesh would have %d vertices; triangles hold int32 vertex numbers (at most "
+                               "2^31 - 1)" % nv)
+        vertices = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+        colors = torch.empty(nv, 3, device=dev, dtype=torch.uint8)
+        triangles = torch.empty(nt, 3, device=dev, dtype=torch.int32)
+        if fill is not None:
+            for t in (vertices, colors, triangles):
+                t.view(torch.uint8).fill_(int(fill))
+        _lib.check(lib.mvster_mesh_emit_vertices(tsdf.data_ptr(), rgb.data_ptr(), has.data_ptr(), o[0], o[1], o[2], voxel, nx, ny, nz,
+                                                 edge_mask.data_ptr(), rank.data_ptr(), offsets[0].data_ptr(), nv,
+                                                 vertices.data_ptr() if nv else None, colors.data_ptr() if nv else None, stream),
+                   "mesh_emit_vertices")
+        _lib.check(lib.mvster_mesh_emit_triangles(tsdf.data_ptr(), weight.data_ptr(), nx, ny, nz, mw, edge_mask.data_ptr(),
+                                                  rank.data_ptr(), offsets[0].data_ptr(), offsets[1].data_ptr(), nv, nt,
+                                                  triangles.data_ptr() if nt else None, stream), "mesh_emit_triangles")
+    return Mesh(vertices, colors, triangles)
+
+
+# ---- a scan's maps to a mesh ------------------------------------------------------------------------------------------------------------
+
+def grid_for_bounds(what, lo, hi, voxel, trunc, memory_budget=MEMORY_BUDGET):
+    """The grid of ``mesh_scene``: the box (lo, hi) padded by ``trunc`` on every side, origin at its low corner, as many nodes
+    per axis as cover it (at least 2) -> (origin, dims).  Refused where the volume and its extraction (``NODE_BYTES`` a node)
+    would take more than ``memory_budget`` bytes or more than 2^31 - 1 nodes; the message names the voxel size that fits."""
+    lo, hi = _check_origin(what, lo), _check_origin(what, hi)
+    if any(h < l for l, h in zip(lo, hi)):
+        raise RuntimeError("%s: bounds must be (lo, hi) with lo <= hi on every axis, not %r, %r" % (what, lo, hi))
+    budget = _number(what, "memory_budget", memory_budget)
+    origin = tuple(l - trunc for l in lo)
+    ext = [(h + trunc) - o for h, o in zip(hi, origin)]
+    dims = tuple(max(2, int(math.ceil(e / voxel)) + 1) for e in ext)
+    nodes = dims[0] * dims[1] * dims[2]
+    cap = min(MAX_NODES, int(budget // NODE_BYTES))
+    if nodes > cap:
+        fit = voxel
+        while True:                                                             # (a few steps of 5%: the count falls with the cube)
+            fit *= 1.05
+            if math.prod(max(2, int(math.ceil(e / fit)) + 1) for e in ext) <= cap:
+                break
+        raise RuntimeError("%s: the volume would hold %d nodes (%d x %d x %d) = %d bytes with its extraction, above the "
+                           "memory_budget of %d bytes (and the limit of 2^31 - 1 nodes); a voxel_size of %g would fit" %
+                           (what, nodes, dims[0], dims[1], dims[2], nodes * NODE_BYTES, int(budget), fit))
+    return origin, dims
+
+
+def _frustum_bounds(depth, mask, views, H, W):
+    """The box of the views' frusta between the least and the greatest used depth of each: a cover of every back-projected
+    pixel.  One read-back (two numbers per view)."""
+    used = (mask != 0) & torch.isfinite(depth) & (depth > 0)
+    big = torch.finfo(torch.float32).max
+    near = torch.where(used, depth, depth.new_full((), big)).flatten(1).amin(1)
+    far = torch.where(used, depth, depth.new_full((), 0.0)).flatten(1).amax(1)
+    ends = torch.stack([near, far], 1).double().cpu().numpy()
+    pts = []
+    for v, (dn, df) in enumerate(ends):
+        if not df > 0:
+            continue
+        K, R, t = views[v, :9].reshape(3, 3), views[v, 9:18].reshape(3, 3), views[v, 18:]
+        corners = np.array([[x, y, 1.0] for x in (-0.5, W - 0.5) for y in (-0.5, H - 0.5)])
+        rays = np.linalg.solve(K, corners.T).T
+        for d in (dn, df):
+            pts.append((rays * d - t) @ R)                                      # R^T (c - t), row-wise
+    if not pts:
+        raise RuntimeError("mesh_scene: no pixel with a usable depth, so there are no bounds; pass bounds=")
+    pts = np.concatenate(pts)
+    return pts.min(0), pts.max(0)
+
+
+def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=None, min_weight=2, memory_budget=MEMORY_BUDGET,
+               device=None, fill=None):
+    """``integrate_tsdf`` then ``extract_mesh`` for the maps of a scan.  ``trunc`` defaults to 4 ``voxel_size`` and is refused
+    below 2 ``voxel_size`` (the ends of a crossing edge could both be clamped).  ``bounds`` = (lo, hi), three numbers each: the
+    grid covers the box padded by ``trunc``, its origin is lo - trunc (``grid_for_bounds``); None: the box of the views' frusta
+    between each view's least and greatest used depth (one more read-back).  A volume above ``memory_budget`` bytes is refused
+    with the voxel size that would fit.  ``min_weight`` (default 2): a node seen by fewer views is unknown.  -> dict:
+    ``vertices``, ``colors``, ``triangles`` (as ``extract_mesh``) and ``volume`` (the ``TSDFVolume``)."""
+    what = "mesh_scene"
+    V, H, W = _check_maps(what, depths, masks, images)
+    views = _cameras(what, Ks, Es, V)
+    voxel = _number(what, "voxel_size", voxel_size)
+    t = _check_trunc(what, voxel, trunc)
+    mw = _check_min_weight(what, min_weight)
+    if bounds is not None:
+        try:
+            lo, hi = bounds
+        except (TypeError, ValueError):
+            raise RuntimeError("%s: bounds must be (lo, hi), not %r" % (what, bounds)) from None
+        origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget)
+    else:
+        _number(what, "memory_budget", memory_budget)
+    dev = _device(what, device, (depths, masks, images))
+    depth = _stack(depths, dev, torch.float32)
+    mask = torch.ones(V, H, W, device=dev, dtype=torch.uint8) if masks is None else _stack(masks, dev, torch.bool).to(torch.uint8)
+    if bounds is None:
+        lo, hi = _frustum_bounds(depth, mask, views, H, W)
+        origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget)
+    vol = integrate_tsdf(depth, mask, images, Ks, Es, origin, voxel, dims, t, device=dev)
+    m = extract_mesh(vol, mw, fill=fill)
+    return dict(vertices=m.vertices, colors=m.colors, triangles=m.triangles, volume=vol)
+
+
+def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene"):
+    """fuse_scene's last step with a ``TSDFMesh``: the reference views' ``depth_est_averaged`` (as float32) under
+    ``final_mask``, their images and cameras through ``mesh_scene``, within the box of the cloud that would be written
+    (``final_*``, else ``thin_*``, else ``points``) -> the ``mesh_*`` keys.  An empty cloud gives an empty mesh."""
+    voxel, trunc, mw = spec
+    pts = res["final_points"] if "final_points" in res else res["thin_points"] if "thin_points" in res else res["points"]
+    dev = pts.device
+    if images.dtype != torch.uint8:                                             # float 0 .. 1: the bytes fuse_scene's colours have
+        images = (images.to(torch.float32) * 255.0).to(torch.int32).to(torch.uint8)
+    idx = torch.as_tensor(np.asarray(ref_views, np.int64), device=dev)
+    if len(pts) == 0:
+        return dict(mesh_vertices=torch.empty(0, 3, device=dev, dtype=torch.float32),
+                    mesh_colors=torch.empty(0, 3, device=dev, dtype=torch.uint8),
+                    mesh_triangles=torch.empty(0, 3, device=dev, dtype=torch.int32), mesh_volume=None)
+    box = torch.stack([pts.amin(0), pts.amax(0)]).double().cpu().numpy()       # one read-back: the cloud's box
+    if not np.isfinite(box).all():
+        raise RuntimeError("%s: the cloud holds a point that is not finite, so the mesh has no bounds" % what)
+    m = mesh_scene(res["depth_est_averaged"].to(torch.float32), res["final_mask"], images[idx], [Ks[int(r)] for r in ref_views],
+                   [Es[int(r)] for r in ref_views], voxel, trunc, (box[0], box[1]), mw, device=dev)
+    vol = m["volume"]
+    return dict(mesh_vertices=m["vertices"], mesh_colors=m["colors"], mesh_triangles=m["triangles"],
+                mesh_volume=dict(vol.params(), min_weight=mw, bounds=(tuple(box[0]), tuple(box[1]))))
+
+
+# ---- files -------------------------------------------------------------------------------------------------------------------------------
+
+PLY_XYZ_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+PLY_XYZRGB_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def write_mesh_ply(filename, vertices, triangles, colors=None):
+    """A triangle mesh as a binary little-endian PLY: ``vertex`` (x y z float, with ``colors`` red green blue uchar) and ``face``
+    (``property list uchar int vertex_indices``, three indices each).  Arrays or tensors; an empty mesh is a valid file."""
+    v, t = _host(vertices), _host(triangles)
+    if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise RuntimeError("write_mesh_ply: vertices must be [Nv,3] and triangles [Nt,3], not %s and %s" % (v.shape, t.shape))
+    if t.size and (t.min() < 0 or t.max() >= len(v)):
+        raise RuntimeError("write_mesh_ply: a triangle names a vertex outside 0 .. %d" % (len(v) - 1))
+    rec = np.empty(len(v), dtype=PLY_XYZ_DTYPE if colors is None else PLY_XYZRGB_DTYPE)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if colors is not None:
+        c = _host(colors)
+        if c.shape != v.shape or c.dtype != np.uint8:
+            raise RuntimeError("write_mesh_ply: colors must be [Nv,3] uint8 with the Nv of vertices, not %s %s" % (c.shape, c.dtype))
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    faces = np.empty(len(t), dtype=PLY_FACE_DTYPE)
+    faces["n"], faces["v"] = 3, t
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(v) + props +
+              "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(t))
+    with open(filename, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(faces.tobytes())
+
+
+def read_mesh_ply(filename):
+    """Inverse of ``write_mesh_ply`` -> (vertices [Nv,3] float32, triangles [Nt,3] int32, colors [Nv,3] uint8 or None)."""
+    with open(filename, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    if "format binary_little_endian 1.0" not in head or "property list uchar int vertex_indices" not in head:
+        raise RuntimeError("read_mesh_ply: only the binary little-endian layout of write_mesh_ply is read")
+    nv = int([l for l in head if l.startswith("element vertex")][0].split()[-1])
+    nt = int([l for l in head if l.startswith("element face")][0].split()[-1])
+    dt = PLY_XYZRGB_DTYPE if "property uchar red" in head else PLY_XYZ_DTYPE
+    rec = np.frombuffer(data[end:end + nv * dt.itemsize], dtype=dt)
+    faces = np.frombuffer(data[end + nv * dt.itemsize:end + nv * dt.itemsize + nt * PLY_FACE_DTYPE.itemsize], dtype=PLY_FACE_DTYPE)
+    if len(rec) != nv or len(faces) != nt or (nt and not (faces["n"] == 3).all()):
+        raise RuntimeError("read_mesh_ply: %s is cut short or holds a face that is not a triangle" % filename)
+    v = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
+    c = np.stack([rec["red"], rec["green"], rec["blue"]], 1).astype(np.uint8) if dt is PLY_XYZRGB_DTYPE else None
+    return v, faces["v"].astype(np.int32).reshape(-1, 3), c
+
+
+def write_result_mesh(filename, res):
+    """The ``mesh_*`` keys of a SceneResult as a PLY."""
+    write_mesh_ply(filename, res["mesh_vertices"], res["mesh_triangles"], res["mesh_colors"])
