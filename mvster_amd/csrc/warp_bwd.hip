@@ -18,7 +18,7 @@ namespace {
 // reference-gradient tile therefore accumulate round(v * 2^k) with integer atomics -- which are also associative, so the
 // sums no longer depend on the order in which the waves arrive -- and are converted back once.  2^k is chosen per
 // launch from upper bounds on the operands (the largest |grad_out|, |ref|, |src|, reduced on the device just before):
-// the largest single contribution lands near 2^36, leaving 27 bits of head room for the number of contributions per
+// the largest single contribution lands below 2^37, leaving 26 bits of head room for the number of contributions per
 // texel and >= 29 bits below the largest value actually seen (fp32 atomics keep 24).
 typedef unsigned long long u64;
 
@@ -36,15 +36,16 @@ __device__ __forceinline__ FixScale make_fix_scale(const float* maxima, int G, i
     const float bound = group ? dcor * fmax / (float)CG : 4.0f * fmax * dcor;
     FixScale f;
     int e = 0;
-    if (bound > 0.0f && bound < INFINITY) frexpf(bound, &e);      // bound < 2^e
-    e = min(max(36 - e, -60), 100);
+    if (bound > 0.0f && bound < INFINITY) frexpf(bound, &e);      // 2^(e-1) <= bound < 2^e
+    e = min(max(37 - e, -60), 100);                               // one unit = 2^(e-37) <= bound * 2^-36, the documented resolution
     f.s = ldexpf(1.0f, e);
     f.inv = ldexpf(1.0f, -e);
     // A non-finite operand (absmax_kernel reports NaN for it) has no fixed-point image: integer conversion would turn it
     // into finite garbage.  Every value converted back then reads NaN instead -- the gradients of such a step are NaN, like
-    // the reference's, never silently finite.  (Resolution otherwise: absolute, bound * 2^-36 per contribution, i.e. the
-    // smallest gradients of a launch keep fewer bits than its largest; fp32 atomics would keep 24 relative to the running sum.)
-    if (!(bound < INFINITY)) { f.s = 0.0f; f.inv = __builtin_nanf(""); }
+    // the reference's, never silently finite (the window forms, whose flush touches only the texels they hit: nan_grad_src
+    // below).  (Resolution otherwise: absolute, at most bound * 2^-36 per contribution, i.e. the smallest gradients of a launch keep fewer bits than its largest; fp32 atomics would keep 24 relative to the running sum.)
+    // (fmaxf above drops a NaN operand: the feature maxima are looked at themselves)
+    if (!(bound < INFINITY) || !(maxima[1] + maxima[2] < INFINITY)) { f.s = 0.0f; f.inv = __builtin_nanf(""); }
     return f;
 }
 // round-to-nearest-even float -> 64-bit integer for |t| < 2^51 in four instructions (the library conversion takes ~12): adding
@@ -160,6 +161,19 @@ struct WarpAggBwdArgs {
     float* rec;             // the records, kRecWords floats each
     int tiles_x, tiles_y;   // source tiles of kRecTileX x kRecTileY texels
 };
+
+// The window forms with a non-finite operand (make_fix_scale: inv is NaN): NaN onto EVERY texel of the batch item's source
+// gradients, the ones no window or tap of this launch reaches included -- as atomic adds, so that they commute with the other
+// workgroups' flushes, and before the gather pass, which adds onto what it finds.  (The sorted form stores every texel through
+// fix_get and needs nothing.)  Workgroup `blk` of `nblk` takes every nblk-th stretch of nthr floats.
+__device__ __forceinline__ void nan_grad_src(const WarpAggBwdArgs& ba, int C, int b, int blk, int nblk, int tid, int nthr, float nan) {
+    const WarpAggArgs& a = ba.f;
+    const long n = (long)a.Hs * a.Ws * C;
+    for (int v = 0; v < a.NV; ++v) {
+        float* g = ba.grad_src + (long)v * a.src_vs + (long)b * a.src_bs;
+        for (long i = (long)blk * nthr + tid; i < n; i += (long)nblk * nthr) unsafeAtomicAdd(g + i, nan);
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // Sorted scatter of the source-view gradient (the adjoint of grid_sample, mvs4net_utils.py:13-59) WITHOUT global atomics.
@@ -589,6 +603,7 @@ __global__ void __launch_bounds__(64 * DMAX) warp_agg_bwd_kernel(WarpAggBwdArgs 
     float* grp = ba.grad_ref + (long)b * a.ref_bs + (long)p0 * C;
     const int npix = min(64, hw - p0);
     for (int i = tid; i < npix * C; i += nthr) grp[i] = fix_get(gref[i % C][i / C], fx.inv);
+    if (!REC && !(fx.inv == fx.inv)) nan_grad_src(ba, C, b, blockIdx.x, gridDim.x, tid, nthr, fx.inv);
 }
 
 // 2-D tile form for the full-resolution stage (C = 8, where this kernel's time is): one workgroup owns 64 columns x R
@@ -788,6 +803,7 @@ __global__ void __launch_bounds__(64 * NW) warp_agg_bwd_tile_kernel(WarpAggBwdAr
         const int npix = min(64, a.w - x0);
         for (int i = tid; i < npix * C; i += nthr) grp[i] = fix_get(gref[r][i % C][i / C], fx.inv);
     }
+    if (!(fx.inv == fx.inv)) nan_grad_src(ba, C, b, blockIdx.x, gridDim.x, tid, nthr, fx.inv);
 }
 
 // Second pass of the atomic-free backward: one workgroup per 32 x 4 tile of one source map; lane = (texel, channel

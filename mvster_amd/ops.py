@@ -452,7 +452,9 @@ def warp_agg_bwd_cl(ref_cl, src_cl, rt, hypo, out, wsum, grad_out, G, group_cor=
     ``into`` = (g_ref, g_src): write into these contiguous buffers instead of allocating; g_src must come zeroed -- except
     with ``sorted_scatter`` (default ``ops.SORTED_SCATTER``; ``mvster_warp_agg_bwd_sorted``: the samples counting-sorted
     by source tile, no global atomics, bit-reproducible, every texel of g_src written exactly once), which ignores what
-    the buffer holds.  Where the sorted form does not apply (huge source maps) the call takes the window form."""
+    the buffer holds.  Where the sorted form does not apply (huge source maps) the call takes the window form.
+    A non-finite value anywhere in ``grad_out``, ``ref_cl`` or ``src_cl`` makes EVERY element of both gradients NaN, in all
+    three forms (the fixed-point counters have no image of it; tests/test_gpu_warp_bwd_exact.py)."""
     import ctypes
     import os
     grad_out = grad_out.contiguous()

@@ -91,8 +91,8 @@ def warp_grid(src_proj, ref_proj, depth_values, Hs, Ws, origin=(0, 0)):
     proj = torch.matmul(src_proj, torch.inverse(ref_proj))
     rot = proj[:, :3, :3]
     trans = proj[:, :3, 3:4]
-    yy, xx = torch.meshgrid(torch.arange(origin[0], origin[0] + Hr, dtype=torch.float32, device=dev),
-                            torch.arange(origin[1], origin[1] + Wr, dtype=torch.float32, device=dev), indexing="ij")
+    yy, xx = torch.meshgrid(torch.arange(origin[0], origin[0] + Hr, dtype=depth_values.dtype, device=dev),
+                            torch.arange(origin[1], origin[1] + Wr, dtype=depth_values.dtype, device=dev), indexing="ij")
     yy = yy.reshape(Hr * Wr)
     xx = xx.reshape(Hr * Wr)
     pix = torch.stack((xx, yy, torch.ones_like(xx))).unsqueeze(0).repeat(B, 1, 1)
