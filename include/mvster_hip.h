@@ -860,6 +860,49 @@ int mvster_mesh_emit_triangles(const float* tsdf, const int* weight, int nx, int
                                const unsigned char* edge_mask, const unsigned short* rank, const long* voffsets,
                                const long* toffsets, long Nv, long Nt, int* triangles, void* stream);
 
+/* ---- cleaning a mesh: weld, components, compaction, vertex normals (csrc/geo_mesh_clean.hip, csrc/mesh_math.h; DESIGN.md
+ * section 4.24).  A mesh is vertices [Nv,3] float32, triangles [Nt,3] int32 with every index in 0 .. Nv-1 (the caller checks
+ * that; the kernels leave a triangle with another index out and never reach out of bounds), Nv and Nt at most 2^29. ---- */
+
+/* The lengths of mvster_mesh_clean_plan's scratch, written to two HOST words: *work_ints (int32 entries; 8 Nv + 2 Nt + 3 B with
+ * B workgroups of 256 over max(Nv, Nt)) and *work_longs (int64 entries; 3 (B + 1) + 8).  MVSTER_ERR_SHAPE for sizes outside
+ * 0 .. 2^29.  The last 8 words of the work_longs buffer are the caller's ONE read-back: Nv', Nt', the components, the canonical
+ * vertices, the triangles dropped, the components kept, the weld table's status (1 = full), and the greatest size key. */
+int mvster_mesh_clean_work(long Nv, long Nt, long* work_ints, long* work_longs);
+/* Workgroups of 256 over Nv vertices: the B of mvster_mesh_vertex_normals' scratch. */
+int mvster_mesh_normals_blocks(long Nv);
+
+/* Everything of a clean-up up to the counts.  weld (0 / 1): vertices whose coordinates compare equal become the one with the
+ * smallest index, through the open-addressing table `table` [2 * table_slots] int32 (table_slots a power of two, >= max(64,
+ * 2 Nv), <= 2^30; not read without weld).  vertices may be NULL without weld (no position is looked at: the components of an
+ * index list).  A triangle with two equal canonical corners, or a corner that is not finite, is dropped; the others fall into
+ * components by shared canonical vertices; a component is kept iff it has >= min_triangles triangles and, with largest_only,
+ * is the one with the most (ties: the smallest root).  -> canon [Nv], labels [Nv] (the smallest vertex of the component; -1
+ * for a vertex no kept triangle uses), tri_labels [Nt], tri_component [Nt] (the row in the table; -1 for a dropped triangle),
+ * and the table roots / comp_vertices / comp_triangles with room for component_rows rows (min(Nv, Nt) always suffices), roots
+ * ascending.  Integer atomics only; the result does not depend on the run.  Nv = 0 or Nt = 0 launches nothing. */
+int mvster_mesh_clean_plan(const float* vertices, const int* triangles, long Nv, long Nt, int weld, long min_triangles,
+                           int largest_only, int* table, long table_slots, int* canon, int* labels, int* tri_labels,
+                           int* tri_component, int* roots, int* comp_vertices, int* comp_triangles, long component_rows,
+                           int* work_ints, long* work_longs, void* stream);
+
+/* The kept vertices (with colors [Nv,3] uint8, or NULL) and triangles, in input order, renumbered, with their input numbers in
+ * vertex_index / triangle_index (int64), from canon and work_ints as mvster_mesh_clean_plan left them.  NvOut /
+ * NtOut: the capacity of the buffers in entries (the counts read back); nothing is written behind them.  One launch; none
+ * where both are 0. */
+int mvster_mesh_clean_emit(const float* vertices, const unsigned char* colors, const int* triangles, long Nv, long Nt,
+                           const int* canon, const int* work_ints, long NvOut, long NtOut,
+                           float* out_vertices, unsigned char* out_colors, int* out_triangles, long* vertex_index,
+                           long* triangle_index, void* stream);
+
+/* Area-weighted vertex normals: normals [Nv,3] float32 and valid [Nv] uint8 (zeros and 0 where the length is 0 or not finite
+ * or no triangle names the vertex).  A vertex sums (b - a) x (c - a) in fp64 over its triangles in ascending triangle index:
+ * work_ints [2 Nv + B] int32, work_longs [B + 1] int64 (B = mvster_mesh_normals_blocks(Nv)) and rows [3 Nt] int32 are scratch
+ * for the vertex -> triangle rows (integer counts, scan, fill, each row put in order by its lane).  No floating-point atomics;
+ * the bytes do not depend on the run.  Nv = 0 launches nothing. */
+int mvster_mesh_vertex_normals(const float* vertices, const int* triangles, long Nv, long Nt, int* work_ints, long* work_longs,
+                               int* rows, float* normals, unsigned char* valid, void* stream);
+
 /* ---- validation pass (csrc/val_ops.hip): test_sample_depth's metrics and its running averages, no host synchronisation ---- */
 
 /* The depth metrics of a batch (utils.py:125-159: AbsDepthError_metrics, Thres_metrics) without boolean-mask gathers: est,

@@ -128,6 +128,11 @@ SIGNATURES = {
     "mvster_mesh_count": [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f],
     "mvster_mesh_emit_vertices": [_f, _f, _f] + [ctypes.c_double] * 4 + [_i, _i, _i, _f, _f, _f, _l, _f, _f, _f],
     "mvster_mesh_emit_triangles": [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _l, _l, _f, _f],
+    "mvster_mesh_clean_work": [_l, _l, _f, _f],
+    "mvster_mesh_clean_plan": [_f, _f, _l, _l, _i, _l, _i, _f, _l] + [_f] * 7 + [_l, _f, _f, _f],
+    "mvster_mesh_normals_blocks": [_l],
+    "mvster_mesh_clean_emit": [_f, _f, _f, _l, _l, _f, _f, _l, _l] + [_f] * 6,
+    "mvster_mesh_vertex_normals": [_f, _f, _l, _l] + [_f] * 6,
     "mvster_depth_metrics_slots": [_l],
     "mvster_depth_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],
     "mvster_pooled_metrics": [_f] * 5 + [_i, _i, _l, _f, _f, _f, _f],

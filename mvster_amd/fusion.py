@@ -20,7 +20,7 @@ import torch
 
 from . import _lib, formats
 from . import mesh as mesh_mod
-from .mesh import TSDFMesh  # noqa: F401  (the ``mesh=`` spec of the scan-level entry points)
+from .mesh import MeshClean, TSDFMesh  # noqa: F401  (the ``mesh=`` / ``mesh_clean=`` specs of the scan-level entry points)
 
 
 def _np32(a):
@@ -860,7 +860,7 @@ def _clean_scene(res, Es, pairs, thinned, outliers, normals):
 
 def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_view, pix_thres=None, rel_thres=None,
                device=None, scratch_budget=SCRATCH_BUDGET, events=None, method="normal", pix_base=PIX_BASE,
-               rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean", outliers=None, normals=None, mesh=None):
+               rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean", outliers=None, normals=None, mesh=None, mesh_clean=None):
     """filter_depth (test_mvs4.py:331-421) for a scan whose maps are in memory.  depths / confidences [V,H,W], images
     [V,H,W,3] (uint8, or float 0..1 as ``read_img`` returns it), Ks [V,3,3], Es [V,4,4]: NumPy arrays, tensors or
     sequences of them, indexed by the view numbers in ``pairs`` [(ref_view, [src_view, ...]), ...].  Tensors already on
@@ -897,11 +897,17 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     over the box of the cloud that would be written (``final_*``, else ``thin_*``, else ``points``) and meshed by marching
     tetrahedra (``mesh.mesh_scene``); the result additionally holds ``mesh_vertices`` [Nv,3] float32,
     ``mesh_colors`` [Nv,3] uint8, ``mesh_triangles`` [Nt,3] int32 and ``mesh_volume`` (the grid: origin, voxel_size, dims,
-    trunc, min_weight, bounds; None for an empty cloud).  Every other key stays byte-equal."""
+    trunc, min_weight, bounds; None for an empty cloud).  Every other key stays byte-equal.
+
+    ``mesh_clean`` (a ``MeshClean(weld=True, min_triangles=0, largest_only=False, normals=False)``, only with ``mesh``; default
+    None: nothing changes and no launch is added): the extracted mesh goes through ``mesh.clean_mesh`` and
+    the ``mesh_*`` keys hold the cleaned mesh, with ``mesh_clean_stats`` and, where normals were asked for, ``mesh_normals``
+    [Nv,3] float32 and ``mesh_normals_valid`` [Nv] uint8."""
     _check_method("fuse_scene", method, pix_thres, rel_thres)
     _check_voxel("fuse_scene", voxel_size, voxel_reduce)
     _check_clean("fuse_scene", outliers, normals)
     mesh_spec = mesh_mod.check_mesh_spec("fuse_scene", mesh)
+    clean_spec = mesh_mod.check_clean_spec("fuse_scene", mesh_clean, mesh)
     dynamic = method == "dynamic"
     pix_thres = PIX_THRES if pix_thres is None else pix_thres
     rel_thres = REL_THRES if rel_thres is None else rel_thres
@@ -1006,7 +1012,7 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     if outliers is not None or normals is not None:
         res.update(_clean_scene(res, Es, pairs, voxel_size is not None, outliers, normals))
     if mesh_spec is not None:
-        res.update(mesh_mod.mesh_fused(res, img, Ks, Es, [r for r, _ in pairs], mesh_spec))
+        res.update(mesh_mod.mesh_fused(res, img, Ks, Es, [r for r, _ in pairs], mesh_spec, clean=clean_spec))
     return res
 
 
@@ -1021,7 +1027,7 @@ def write_scene_ply(filename, res, thinned=False):
 
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, thres_view=5, device="cuda:0",
                  filter_method="normal", pix_base=PIX_BASE, rel_base=REL_BASE, voxel_size=None, voxel_reduce="mean",
-                 outliers=None, normals=None, mesh=None, meshfilename=None):
+                 outliers=None, normals=None, mesh=None, meshfilename=None, mesh_clean=None):
     """The reference's ``filter_depth`` (test_mvs4.py:331-421; its ``args.conf`` / ``args.thres_view`` are keywords
     here): reads ``pair_folder/pair.txt``, ``scan_folder/cams/{:0>8}_cam.txt`` and ``images/{:0>8}.jpg``,
     ``out_folder/depth_est/{:0>8}.pfm`` and ``confidence/{:0>8}.pfm`` -- every file once --, fuses the scan on the GPU and
@@ -1031,11 +1037,13 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, th
     (``thin_points`` with ``voxel_reduce``).  ``outliers`` / ``normals``: as ``fuse_scene``; the cloud written and returned is
     then the cleaned one, with nx ny nz in the file where normals were asked for.  ``mesh`` (a ``TSDFMesh``): as ``fuse_scene``;
     the triangle mesh is written to ``meshfilename`` (``mesh.write_mesh_ply``), which is required then and refused without
-    ``mesh``.  -> the vertex array."""
+    ``mesh``.  ``mesh_clean`` (a ``MeshClean``, only with ``mesh``): as ``fuse_scene``; the mesh written is the cleaned one, with
+    nx ny nz in the file where normals were asked for.  -> the vertex array."""
     _check_method("filter_depth", filter_method)
     _check_voxel("filter_depth", voxel_size, voxel_reduce)
     _check_clean("filter_depth", outliers, normals)
     mesh_mod.check_mesh_spec("filter_depth", mesh)
+    mesh_mod.check_clean_spec("filter_depth", mesh_clean, mesh)
     if (mesh is None) != (meshfilename is None):
         raise RuntimeError("filter_depth: mesh and meshfilename go together (a TSDFMesh and the file its mesh is written to)")
     try:
@@ -1057,7 +1065,7 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=0.9, th
     res = fuse_scene(depths, confs, images, [c[0] for c in cams], [c[1] for c in cams],
                      [(slot[r], [slot[v] for v in srcs]) for r, srcs in pairs], conf, thres_view, device=device,
                      method=filter_method, pix_base=pix_base, rel_base=rel_base, voxel_size=voxel_size,
-                     voxel_reduce=voxel_reduce, outliers=outliers, normals=normals, mesh=mesh)
+                     voxel_reduce=voxel_reduce, outliers=outliers, normals=normals, mesh=mesh, mesh_clean=mesh_clean)
     if mesh is not None:
         mesh_mod.write_result_mesh(meshfilename, res)
     os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)

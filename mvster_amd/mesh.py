@@ -8,6 +8,7 @@ project's own definition, modelled on KinectFusion / Open3D-style integration: n
 along z, unit weights, a dense grid.  Open3D is not at hand, so agreement with it is untested.  There is no CPU fallback.
 """
 import collections
+import ctypes
 import math
 
 import numpy as np
@@ -24,6 +25,11 @@ DEFAULT_TRUNC_VOXELS = 4.0
 
 TSDFMesh = collections.namedtuple("TSDFMesh", "voxel_size trunc min_weight", defaults=(None, 2))
 Mesh = collections.namedtuple("Mesh", "vertices colors triangles")
+# the ``mesh_clean=`` spec of the scan-level entry points (a keyword of its own: TSDFMesh(0.01) == (0.01, None, 2) is pinned)
+MeshClean = collections.namedtuple("MeshClean", "weld min_triangles largest_only normals", defaults=(True, 0, False, False))
+
+MAX_CLEAN_VERTICES = 1 << 29            # mesh::kMaxVertices: the weld table holds at most 2^30 slots, two per vertex
+MAX_CLEAN_TRIANGLES = 1 << 29           # mesh::kMaxTriangles: 3 Nt corners are counted in 32 bits
 
 
 class TSDFVolume:
@@ -333,14 +339,17 @@ def _frustum_bounds(depth, mask, views, H, W):
 
 
 def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=None, min_weight=2, memory_budget=MEMORY_BUDGET,
-               device=None, fill=None):
+               device=None, fill=None, mesh_clean=None):
     """``integrate_tsdf`` then ``extract_mesh`` for the maps of a scan.  ``trunc`` defaults to 4 ``voxel_size`` and is refused
     below 2 ``voxel_size`` (the ends of a crossing edge could both be clamped).  ``bounds`` = (lo, hi), three numbers each: the
     grid covers the box padded by ``trunc``, its origin is lo - trunc (``grid_for_bounds``); None: the box of the views' frusta
     between each view's least and greatest used depth (one more read-back).  A volume above ``memory_budget`` bytes is refused
     with the voxel size that would fit.  ``min_weight`` (default 2): a node seen by fewer views is unknown.  -> dict:
-    ``vertices``, ``colors``, ``triangles`` (as ``extract_mesh``) and ``volume`` (the ``TSDFVolume``)."""
+    ``vertices``, ``colors``, ``triangles`` (as ``extract_mesh``) and ``volume`` (the ``TSDFVolume``).  ``mesh_clean`` (a
+    ``MeshClean``; default None: nothing changes and no launch is added): the extracted mesh goes through ``clean_mesh`` and
+    the three keys hold the cleaned mesh, with ``clean_stats`` and, where asked for, ``normals`` / ``normals_valid``."""
     what = "mesh_scene"
+    clean = check_clean_spec(what, mesh_clean)
     V, H, W = _check_maps(what, depths, masks, images)
     views = _cameras(what, Ks, Es, V)
     voxel = _number(what, "voxel_size", voxel_size)
@@ -362,13 +371,27 @@ def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=Non
         origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget)
     vol = integrate_tsdf(depth, mask, images, Ks, Es, origin, voxel, dims, t, device=dev)
     m = extract_mesh(vol, mw, fill=fill)
-    return dict(vertices=m.vertices, colors=m.colors, triangles=m.triangles, volume=vol)
+    out = dict(vertices=m.vertices, colors=m.colors, triangles=m.triangles, volume=vol)
+    if clean is not None:
+        out.update(_cleaned_keys(clean_mesh(m.vertices, m.triangles, m.colors, *clean, fill=fill, _checked=True), clean, ""))
+    return out
 
 
-def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene"):
+def _cleaned_keys(c, clean, prefix):
+    """What a ``MeshClean`` adds to a result: the cleaned mesh over the three mesh keys, its statistics, its normals if asked."""
+    out = {prefix + "vertices": c["vertices"], prefix + "colors": c["colors"], prefix + "triangles": c["triangles"],
+           prefix + "clean_stats": c["stats"]}
+    if clean.normals:
+        out[prefix + "normals"], out[prefix + "normals_valid"] = c["normals"], c["normals_valid"]
+    return out
+
+
+def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene", clean=None):
     """fuse_scene's last step with a ``TSDFMesh``: the reference views' ``depth_est_averaged`` (as float32) under
     ``final_mask``, their images and cameras through ``mesh_scene``, within the box of the cloud that would be written
-    (``final_*``, else ``thin_*``, else ``points``) -> the ``mesh_*`` keys.  An empty cloud gives an empty mesh."""
+    (``final_*``, else ``thin_*``, else ``points``) -> the ``mesh_*`` keys.  An empty cloud gives an empty mesh.  ``clean`` (a
+    checked ``MeshClean``): the mesh goes through ``clean_mesh``; the ``mesh_*`` keys hold the cleaned mesh, with
+    ``mesh_clean_stats`` and, where asked for, ``mesh_normals`` / ``mesh_normals_valid``."""
     voxel, trunc, mw = spec
     pts = res["final_points"] if "final_points" in res else res["thin_points"] if "thin_points" in res else res["points"]
     dev = pts.device
@@ -376,23 +399,259 @@ def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene"):
         images = (images.to(torch.float32) * 255.0).to(torch.int32).to(torch.uint8)
     idx = torch.as_tensor(np.asarray(ref_views, np.int64), device=dev)
     if len(pts) == 0:
-        return dict(mesh_vertices=torch.empty(0, 3, device=dev, dtype=torch.float32),
-                    mesh_colors=torch.empty(0, 3, device=dev, dtype=torch.uint8),
-                    mesh_triangles=torch.empty(0, 3, device=dev, dtype=torch.int32), mesh_volume=None)
+        out = dict(mesh_vertices=torch.empty(0, 3, device=dev, dtype=torch.float32),
+                   mesh_colors=torch.empty(0, 3, device=dev, dtype=torch.uint8),
+                   mesh_triangles=torch.empty(0, 3, device=dev, dtype=torch.int32), mesh_volume=None)
+        if clean is not None:
+            out.update(_cleaned_keys(clean_mesh(out["mesh_vertices"], out["mesh_triangles"], out["mesh_colors"], *clean, _checked=True),
+                                     clean, "mesh_"))
+        return out
     box = torch.stack([pts.amin(0), pts.amax(0)]).double().cpu().numpy()       # one read-back: the cloud's box
     if not np.isfinite(box).all():
         raise RuntimeError("%s: the cloud holds a point that is not finite, so the mesh has no bounds" % what)
     m = mesh_scene(res["depth_est_averaged"].to(torch.float32), res["final_mask"], images[idx], [Ks[int(r)] for r in ref_views],
                    [Es[int(r)] for r in ref_views], voxel, trunc, (box[0], box[1]), mw, device=dev)
     vol = m["volume"]
-    return dict(mesh_vertices=m["vertices"], mesh_colors=m["colors"], mesh_triangles=m["triangles"],
-                mesh_volume=dict(vol.params(), min_weight=mw, bounds=(tuple(box[0]), tuple(box[1]))))
+    out = dict(mesh_vertices=m["vertices"], mesh_colors=m["colors"], mesh_triangles=m["triangles"],
+               mesh_volume=dict(vol.params(), min_weight=mw, bounds=(tuple(box[0]), tuple(box[1]))))
+    if clean is not None:
+        out.update(_cleaned_keys(clean_mesh(m["vertices"], m["triangles"], m["colors"], *clean, _checked=True), clean, "mesh_"))
+    return out
+
+
+# ---- cleaning a mesh ------------------------------------------------------------------------------------------------------------------
+
+def _flag(what, name, value):
+    if not isinstance(value, (bool, np.bool_)):
+        raise RuntimeError("%s: %s must be True or False, not %r" % (what, name, value))
+    return bool(value)
+
+
+def _check_min_triangles(what, min_triangles):
+    if isinstance(min_triangles, (bool, np.bool_)) or not isinstance(min_triangles, (int, np.integer)) or \
+            not 0 <= int(min_triangles) < (1 << 31):
+        raise RuntimeError("%s: min_triangles must be an integer >= 0 (and below 2^31), not %r" % (what, min_triangles))
+    return int(min_triangles)
+
+
+def check_clean_spec(what, mesh_clean, mesh=True):
+    """The ``mesh_clean`` keyword of the scan-level entry points, checked before anything runs -> a ``MeshClean`` of plain Python
+    values, or None.  ``mesh``: the call's ``mesh=`` keyword (a ``MeshClean`` without a mesh to clean is refused)."""
+    if mesh_clean is None:
+        return None
+    if not isinstance(mesh_clean, MeshClean):
+        raise RuntimeError("%s: mesh_clean must be None or a MeshClean, not %r" % (what, mesh_clean))
+    if mesh is None:
+        raise RuntimeError("%s: mesh_clean needs mesh= (a TSDFMesh): there is no mesh to clean" % what)
+    return MeshClean(_flag(what, "mesh_clean.weld", mesh_clean.weld), _check_min_triangles(what, mesh_clean.min_triangles),
+                     _flag(what, "mesh_clean.largest_only", mesh_clean.largest_only), _flag(what, "mesh_clean.normals", mesh_clean.normals))
+
+
+def clean_slots(n_vertices):
+    """The smallest weld table ``clean_mesh`` takes: a power of two, at least max(64, 2 * Nv) slots."""
+    return max(64, 1 << max(0, 2 * int(n_vertices) - 1).bit_length())
+
+
+def _check_triangles(what, triangles, n_vertices, checked=False):
+    """triangles [Nt,3] int32 with every index in 0 .. n_vertices - 1 (one read-back of the least and the greatest index, before
+    any launch of the library; ``checked``: the mesh is ``extract_mesh``'s own and the look is left out) -> Nt"""
+    if not isinstance(triangles, torch.Tensor) or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise RuntimeError("%s: triangles must be an int32 tensor [Nt,3], not %s" %
+                           (what, (tuple(triangles.shape), triangles.dtype) if isinstance(triangles, torch.Tensor) else type(triangles).__name__))
+    nt = triangles.shape[0]
+    if nt > MAX_CLEAN_TRIANGLES:
+        raise RuntimeError("%s: at most 2^29 triangles, not %d" % (what, nt))
+    if nt and not checked:
+        lo, hi = (int(x) for x in torch.stack(torch.aminmax(triangles)).cpu())
+        if lo < 0 or hi >= n_vertices:
+            raise RuntimeError("%s: a triangle names vertex %d, outside 0 .. %d" % (what, lo if lo < 0 else hi, n_vertices - 1))
+    return nt
+
+
+def _check_vertices(what, vertices, colors=None):
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise RuntimeError("%s: vertices must be a float32 tensor [Nv,3], not %s" %
+                           (what, (tuple(vertices.shape), vertices.dtype) if isinstance(vertices, torch.Tensor) else type(vertices).__name__))
+    if vertices.shape[0] > MAX_CLEAN_VERTICES:
+        raise RuntimeError("%s: at most 2^29 vertices, not %d" % (what, vertices.shape[0]))
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.shape != vertices.shape or colors.dtype != torch.uint8):
+        raise RuntimeError("%s: colors must be a uint8 tensor [Nv,3] with the Nv of vertices" % what)
+    return vertices.shape[0]
+
+
+def _on_gpu(what, *tensors):
+    ts = [t for t in tensors if t is not None]
+    if not all(t.is_cuda and t.device == ts[0].device for t in ts):
+        raise RuntimeError("mvster_amd.mesh.%s runs on MI355X only: its tensors must be on one GPU (there is no CPU fallback)" % what)
+    return ts[0].device
+
+
+class _CleanPlan:
+    """``mvster_mesh_clean_plan`` run on a mesh and its ONE read-back: ``canon``, ``labels`` [Nv], ``tri_labels``,
+    ``tri_component`` [Nt], ``roots``, ``comp_vertices``, ``comp_triangles`` [components] on the GPU, and as Python ints
+    ``nv_out``, ``nt_out``, ``components``, ``canonical``, ``dropped``, ``kept``.  ``emit`` writes the compacted mesh."""
+
+    def __init__(self, what, vertices, triangles, n_vertices, weld, min_triangles, largest_only, slots):
+        lib = _lib.load()
+        dev = triangles.device
+        self.vertices, self.triangles = vertices, triangles.contiguous()
+        nv, nt = self.nv, self.nt = n_vertices, triangles.shape[0]
+        rows = min(nv, nt)
+        i32 = dict(device=dev, dtype=torch.int32)
+        with torch.cuda.device(dev):
+            self.stream = torch.cuda.current_stream(dev).cuda_stream
+            self.canon, self.labels = torch.empty(nv, **i32), torch.empty(nv, **i32)
+            self.tri_labels, self.tri_component = torch.empty(nt, **i32), torch.empty(nt, **i32)
+            table = torch.empty(2 * slots, **i32) if weld else None
+            comp = torch.empty(3, rows, **i32)
+            n_ints, n_longs = ctypes.c_long(), ctypes.c_long()
+            _lib.check(lib.mvster_mesh_clean_work(nv, nt, ctypes.byref(n_ints), ctypes.byref(n_longs)), "mesh_clean_work")
+            self.work_ints = torch.empty(n_ints.value, **i32)
+            self.work_longs = torch.empty(n_longs.value, device=dev, dtype=torch.int64)
+            _lib.check(lib.mvster_mesh_clean_plan(None if vertices is None else self.vertices.data_ptr(), self.triangles.data_ptr(), nv,
+                                                  nt, int(weld), min_triangles, int(largest_only),
+                                                  table.data_ptr() if weld else None, slots if weld else 0, self.canon.data_ptr(),
+                                                  self.labels.data_ptr(), self.tri_labels.data_ptr(), self.tri_component.data_ptr(),
+                                                  comp[0].data_ptr(), comp[1].data_ptr(), comp[2].data_ptr(), rows,
+                                                  self.work_ints.data_ptr(), self.work_longs.data_ptr(), self.stream), "mesh_clean_plan")
+            stats = [int(x) for x in self.work_longs[-8:].cpu()]                   # the one read-back: counts and status
+        self.nv_out, self.nt_out, self.components, self.canonical, self.dropped, self.kept, status = stats[:7]
+        if status:
+            raise RuntimeError("%s: the weld table of %d slots is full (this cannot happen at the enforced size)" % (what, slots))
+        self.roots, self.comp_vertices, self.comp_triangles = (comp[k, :self.components] for k in range(3))
+
+    def emit(self, colors, vertices, out_colors, triangles, vertex_index, triangle_index, nv_out=None, nt_out=None):
+        """The kept vertices and triangles into the caller's buffers (``nv_out`` / ``nt_out``: their capacity in entries)."""
+        nv_out = self.nv_out if nv_out is None else nv_out
+        nt_out = self.nt_out if nt_out is None else nt_out
+        with torch.cuda.device(self.triangles.device):
+            _lib.check(_lib.load().mvster_mesh_clean_emit(
+                self.vertices.data_ptr(), None if colors is None else colors.data_ptr(), self.triangles.data_ptr(), self.nv, self.nt,
+                self.canon.data_ptr(), self.work_ints.data_ptr(), nv_out, nt_out,
+                vertices.data_ptr() if nv_out else None, out_colors.data_ptr() if nv_out and colors is not None else None,
+                triangles.data_ptr() if nt_out else None, vertex_index.data_ptr() if nv_out else None,
+                triangle_index.data_ptr() if nt_out else None, self.stream), "mesh_clean_emit")
+
+
+def mesh_components(triangles, n_vertices):
+    """The connected components of a triangle list on the GPU (defined exactly in
+    mvster_amd/csrc/mesh_math.h): ``triangles`` [Nt,3] int32 on the GPU with every index in 0 .. ``n_vertices`` - 1.  A triangle
+    that names a vertex twice is dropped; two others are connected if they share a vertex (vertex connectivity: Open3D's
+    ``cluster_connected_triangles`` connects across shared edges only).  -> dict of GPU tensors: ``labels`` [n_vertices] int32 =
+    the smallest vertex of a vertex's component (-1 for a vertex no kept triangle names), ``tri_labels`` [Nt] int32 (-1 for a
+    dropped triangle), ``tri_component`` [Nt] int32 = the row of the triangle's component in the table, and the table in
+    ascending order of ``roots`` [C] int32 with ``n_vertices`` / ``n_triangles`` [C] int32.  Lock-free union-find with integer
+    atomics: the result does not depend on the run.  One read-back (C) besides the look at the index range.  No CPU fallback."""
+    what = "mesh_components"
+    if isinstance(n_vertices, (bool, np.bool_)) or not isinstance(n_vertices, (int, np.integer)) or \
+            not 0 <= int(n_vertices) <= MAX_CLEAN_VERTICES:
+        raise RuntimeError("%s: n_vertices must be an integer in 0 .. 2^29, not %r" % (what, n_vertices))
+    nv = int(n_vertices)
+    nt = _check_triangles(what, triangles, nv)
+    dev = _on_gpu(what, triangles)
+    if nv == 0 or nt == 0:
+        e = torch.empty(0, device=dev, dtype=torch.int32)
+        return dict(labels=torch.full((nv,), -1, device=dev, dtype=torch.int32), tri_labels=e, tri_component=e.clone(), roots=e.clone(),
+                    n_vertices=e.clone(), n_triangles=e.clone())
+    p = _CleanPlan(what, None, triangles, nv, False, 0, False, 0)
+    return dict(labels=p.labels, tri_labels=p.tri_labels, tri_component=p.tri_component, roots=p.roots, n_vertices=p.comp_vertices,
+                n_triangles=p.comp_triangles)
+
+
+def vertex_normals(vertices, triangles, fill=None, _checked=False):
+    """Area-weighted vertex normals on the GPU (defined exactly in mvster_amd/csrc/mesh_math.h):
+    ``vertices`` [Nv,3] float32 and ``triangles`` [Nt,3] int32 on the GPU.  With the positions widened to fp64, a triangle
+    (a, b, c) gives n_t = (b - a) x (c - a); a vertex's N is the sum of n_t over the triangles that name it in ascending triangle
+    index (once per occurrence), its normal (float)(N / |N|).  -> dict: ``normals`` [Nv,3] float32 and ``valid`` [Nv] uint8:
+    zeros and 0 where |N| is 0 or not finite or no triangle names the vertex.  The normal follows the winding; for
+    ``extract_mesh`` output it points to the free-space side.  This is the project's own definition (Open3D sums unit triangle
+    normals).  The order of every sum is fixed (vertex -> triangle rows put into ascending order): no floating-point atomics,
+    two runs give the same bytes.  No read-back besides the look at the index range.  ``fill`` (tests): a byte the outputs are
+    filled with before the kernels write them.  No CPU fallback."""
+    what = "vertex_normals"
+    nv = _check_vertices(what, vertices)
+    nt = _check_triangles(what, triangles, nv, _checked)
+    dev = _on_gpu(what, vertices, triangles)
+    if nv == 0 or nt == 0:
+        return dict(normals=torch.zeros(nv, 3, device=dev, dtype=torch.float32), valid=torch.zeros(nv, device=dev, dtype=torch.uint8))
+    vertices, triangles = vertices.contiguous(), triangles.contiguous()
+    normals = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+    valid = torch.empty(nv, device=dev, dtype=torch.uint8)
+    if fill is not None:
+        normals.view(torch.uint8).fill_(int(fill))
+        valid.fill_(int(fill))
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        blocks = lib.mvster_mesh_normals_blocks(nv)
+        work_ints = torch.empty(2 * nv + blocks, device=dev, dtype=torch.int32)
+        work_longs = torch.empty(blocks + 1, device=dev, dtype=torch.int64)
+        rows = torch.empty(3 * nt, device=dev, dtype=torch.int32)
+        _lib.check(lib.mvster_mesh_vertex_normals(vertices.data_ptr(), triangles.data_ptr(), nv, nt, work_ints.data_ptr(),
+                                                  work_longs.data_ptr(), rows.data_ptr(), normals.data_ptr(), valid.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream), "mesh_vertex_normals")
+    return dict(normals=normals, valid=valid)
+
+
+def clean_mesh(vertices, triangles, colors=None, weld=True, min_triangles=0, largest_only=False, normals=False, table_slots=None,
+               fill=None, _checked=False):
+    """A mesh cleaned on the GPU (defined exactly in mvster_amd/csrc/mesh_math.h): ``vertices`` [Nv,3]
+    float32, ``triangles`` [Nt,3] int32 (every index in 0 .. Nv-1) and optionally ``colors`` [Nv,3] uint8, tensors on the GPU.  In
+    this order: ``weld``: vertices whose three coordinates compare equal (-0.0 equals 0.0; one that is not finite equals
+    nothing) become the one with the smallest index, which keeps its own position and colour; a triangle with two equal corners
+    after that, or with a corner that is not finite, is dropped (collinear ones with three distinct corners are kept, duplicate
+    triangles are not looked for); the rest fall into components by shared vertices (``mesh_components``); a component is kept
+    iff it has at least ``min_triangles`` triangles and, with ``largest_only``, is the one with the most (ties: the one with the
+    smallest vertex); the kept triangles stay in input order, the vertices they use (canonical ones) stay in input order, and the
+    indices are renumbered.  -> dict: ``vertices`` [Nv',3], ``colors`` [Nv',3] (None without ``colors``), ``triangles``
+    [Nt',3], ``vertex_index`` [Nv'] and ``triangle_index`` [Nt'] int64 into the input; with ``normals``: ``normals`` [Nv',3]
+    float32 and ``normals_valid`` [Nv'] uint8, ``vertex_normals`` of the cleaned mesh; ``stats``: ``welded`` (vertices that
+    coincide with an earlier one), ``degenerate`` (triangles dropped), ``components``, ``components_kept``,
+    ``triangles_removed``, ``vertices_removed`` (Python ints).  Integer atomics only and fixed sum orders: two runs give the same
+    bytes, whatever ``table_slots`` (the weld's hash table: a power of two >= max(64, 2 * Nv), default the smallest).  One
+    read-back holds the counts and the table's status; the public call looks at the index range before (one more).  An empty
+    input (Nv = 0 or Nt = 0) launches nothing and gives an empty mesh.  ``fill`` (tests): a byte the outputs are filled with
+    before the kernels write them.  No CPU fallback."""
+    what = "clean_mesh"
+    weld, largest_only, normals = _flag(what, "weld", weld), _flag(what, "largest_only", largest_only), _flag(what, "normals", normals)
+    min_triangles = _check_min_triangles(what, min_triangles)
+    nv = _check_vertices(what, vertices, colors)
+    slots = clean_slots(nv) if table_slots is None else table_slots
+    if isinstance(slots, bool) or not isinstance(slots, int) or slots < clean_slots(nv) or slots & (slots - 1) or slots > 1 << 30:
+        raise RuntimeError("%s: table_slots must be a power of two, >= max(64, 2 * Nv) = %d and <= 2^30, not %r" %
+                           (what, max(64, 2 * nv), table_slots))
+    nt = _check_triangles(what, triangles, nv, _checked)
+    dev = _on_gpu(what, vertices, triangles, colors)
+    if nv == 0 or nt == 0:
+        nvo, nto, plan = 0, 0, None
+        stats = dict(welded=0, degenerate=0, components=0, components_kept=0)
+    else:
+        vertices = vertices.contiguous()
+        colors = None if colors is None else colors.contiguous()
+        plan = _CleanPlan(what, vertices, triangles, nv, weld, min_triangles, largest_only, slots)
+        nvo, nto = plan.nv_out, plan.nt_out
+        stats = dict(welded=nv - plan.canonical, degenerate=plan.dropped, components=plan.components, components_kept=plan.kept)
+    stats.update(triangles_removed=nt - nto, vertices_removed=nv - nvo)
+    out = dict(vertices=torch.empty(nvo, 3, device=dev, dtype=torch.float32),
+               colors=None if colors is None else torch.empty(nvo, 3, device=dev, dtype=torch.uint8),
+               triangles=torch.empty(nto, 3, device=dev, dtype=torch.int32), vertex_index=torch.empty(nvo, device=dev, dtype=torch.int64),
+               triangle_index=torch.empty(nto, device=dev, dtype=torch.int64), stats=stats)
+    if fill is not None:
+        for k in ("vertices", "colors", "triangles", "vertex_index", "triangle_index"):
+            if out[k] is not None:
+                out[k].view(torch.uint8).fill_(int(fill))
+    if plan is not None:
+        plan.emit(colors, out["vertices"], out["colors"], out["triangles"], out["vertex_index"], out["triangle_index"])
+    if normals:
+        n = vertex_normals(out["vertices"], out["triangles"], fill=fill, _checked=True)
+        out["normals"], out["normals_valid"] = n["normals"], n["valid"]
+    return out
 
 
 # ---- files -------------------------------------------------------------------------------------------------------------------------------
 
 PLY_XYZ_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 PLY_XYZRGB_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+PLY_NORMAL_FIELDS = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
 PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
@@ -400,17 +659,30 @@ def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def write_mesh_ply(filename, vertices, triangles, colors=None):
-    """A triangle mesh as a binary little-endian PLY: ``vertex`` (x y z float, with ``colors`` red green blue uchar) and ``face``
-    (``property list uchar int vertex_indices``, three indices each).  Arrays or tensors; an empty mesh is a valid file."""
+def _ply_vertex_dtype(with_normals, with_colors):
+    if not with_normals:
+        return PLY_XYZRGB_DTYPE if with_colors else PLY_XYZ_DTYPE
+    return np.dtype(PLY_XYZ_DTYPE.descr + PLY_NORMAL_FIELDS + (PLY_XYZRGB_DTYPE.descr[3:] if with_colors else []))
+
+
+def write_mesh_ply(filename, vertices, triangles, colors=None, normals=None):
+    """A triangle mesh as a binary little-endian PLY: ``vertex`` (x y z float, with ``normals`` nx ny nz float behind them, with
+    ``colors`` red green blue uchar last) and ``face`` (``property list uchar int vertex_indices``, three indices each).  Arrays
+    or tensors; an empty mesh is a valid file."""
     v, t = _host(vertices), _host(triangles)
     if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
         raise RuntimeError("write_mesh_ply: vertices must be [Nv,3] and triangles [Nt,3], not %s and %s" % (v.shape, t.shape))
     if t.size and (t.min() < 0 or t.max() >= len(v)):
         raise RuntimeError("write_mesh_ply: a triangle names a vertex outside 0 .. %d" % (len(v) - 1))
-    rec = np.empty(len(v), dtype=PLY_XYZ_DTYPE if colors is None else PLY_XYZRGB_DTYPE)
+    rec = np.empty(len(v), dtype=_ply_vertex_dtype(normals is not None, colors is not None))
     rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
     props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        n = _host(normals)
+        if n.shape != v.shape or n.dtype != np.float32:
+            raise RuntimeError("write_mesh_ply: normals must be [Nv,3] float32 with the Nv of vertices, not %s %s" % (n.shape, n.dtype))
+        rec["nx"], rec["ny"], rec["nz"] = n[:, 0], n[:, 1], n[:, 2]
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         c = _host(colors)
         if c.shape != v.shape or c.dtype != np.uint8:
@@ -427,8 +699,9 @@ def write_mesh_ply(filename, vertices, triangles, colors=None):
         f.write(faces.tobytes())
 
 
-def read_mesh_ply(filename):
-    """Inverse of ``write_mesh_ply`` -> (vertices [Nv,3] float32, triangles [Nt,3] int32, colors [Nv,3] uint8 or None)."""
+def read_mesh_ply(filename, with_normals=False):
+    """Inverse of ``write_mesh_ply`` -> (vertices [Nv,3] float32, triangles [Nt,3] int32, colors [Nv,3] uint8 or None); with
+    ``with_normals`` a fourth entry, normals [Nv,3] float32 or None.  A file with normals is read either way."""
     with open(filename, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -437,16 +710,21 @@ def read_mesh_ply(filename):
         raise RuntimeError("read_mesh_ply: only the binary little-endian layout of write_mesh_ply is read")
     nv = int([l for l in head if l.startswith("element vertex")][0].split()[-1])
     nt = int([l for l in head if l.startswith("element face")][0].split()[-1])
-    dt = PLY_XYZRGB_DTYPE if "property uchar red" in head else PLY_XYZ_DTYPE
+    has_normals, has_colors = "property float nx" in head, "property uchar red" in head
+    dt = _ply_vertex_dtype(has_normals, has_colors)
     rec = np.frombuffer(data[end:end + nv * dt.itemsize], dtype=dt)
     faces = np.frombuffer(data[end + nv * dt.itemsize:end + nv * dt.itemsize + nt * PLY_FACE_DTYPE.itemsize], dtype=PLY_FACE_DTYPE)
     if len(rec) != nv or len(faces) != nt or (nt and not (faces["n"] == 3).all()):
         raise RuntimeError("read_mesh_ply: %s is cut short or holds a face that is not a triangle" % filename)
     v = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
-    c = np.stack([rec["red"], rec["green"], rec["blue"]], 1).astype(np.uint8) if dt is PLY_XYZRGB_DTYPE else None
-    return v, faces["v"].astype(np.int32).reshape(-1, 3), c
+    c = np.stack([rec["red"], rec["green"], rec["blue"]], 1).astype(np.uint8) if has_colors else None
+    out = (v, faces["v"].astype(np.int32).reshape(-1, 3), c)
+    if with_normals:
+        out += (np.stack([rec["nx"], rec["ny"], rec["nz"]], 1).astype(np.float32) if has_normals else None,)
+    return out
 
 
 def write_result_mesh(filename, res):
-    """The ``mesh_*`` keys of a SceneResult as a PLY."""
-    write_mesh_ply(filename, res["mesh_vertices"], res["mesh_triangles"], res["mesh_colors"])
+    """The ``mesh_*`` keys of a SceneResult as a PLY, with ``mesh_normals`` where the result has them."""
+    write_mesh_ply(filename, res["mesh_vertices"], res["mesh_triangles"], res["mesh_colors"],
+                   res["mesh_normals"] if "mesh_normals" in res else None)

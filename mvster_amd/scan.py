@@ -771,7 +771,7 @@ def write_scan_outputs(result, images, out_folder):
 
 def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres_view=5, plyfilename=None, short_sources=None,
                      fusion="normal", pix_base=None, rel_base=None, voxel_size=None, voxel_reduce="mean", outliers=None, normals=None,
-                     mesh=None, meshfilename=None, **kw):
+                     mesh=None, meshfilename=None, mesh_clean=None, **kw):
     """``infer_scan`` followed by ``fusion.fuse_scene`` on the device tensors: the reference's ``save_scene_depth`` +
     ``filter_depth`` (test_mvs4.py:170-268, :331-421) without leaving the GPU.  -> the ``fusion.SceneResult`` (with the
     ``ScanResult`` as its ``scan`` attribute); writes the point cloud to ``plyfilename`` if given.
@@ -789,14 +789,16 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     ``outliers`` / ``normals``: as ``fuse_scene`` (outlier removal and normals on the cloud that would be written); the
     result then holds the ``final_*`` cloud, and that is the one written, with its normals.  ``mesh`` (a
     ``fusion.TSDFMesh``): as ``fuse_scene`` (TSDF integration of the filtered maps and marching tetrahedra; the result then
-    holds the ``mesh_*`` keys); ``meshfilename``: the triangle mesh is written there (only with ``mesh``).  Neither reaches
-    ``infer_scan``; with the default None nothing changes."""
+    holds the ``mesh_*`` keys); ``meshfilename``: the triangle mesh is written there (only with ``mesh``); ``mesh_clean`` (a
+    ``fusion.MeshClean``, only with ``mesh``): as ``fuse_scene`` (the ``mesh_*`` keys and the file hold the cleaned mesh, with its
+    normals where asked for).  None of them reaches ``infer_scan``; with the default None nothing changes."""
     from . import fusion as fusion_mod
     from . import mesh as mesh_mod
     fusion_mod._check_method("reconstruct_scan", fusion)
     fusion_mod._check_voxel("reconstruct_scan", voxel_size, voxel_reduce)
     fusion_mod._check_clean("reconstruct_scan", outliers, normals)
     mesh_mod.check_mesh_spec("reconstruct_scan", mesh)
+    mesh_mod.check_clean_spec("reconstruct_scan", mesh_clean, mesh)
     if meshfilename is not None and mesh is None:
         raise RuntimeError("reconstruct_scan: meshfilename needs mesh= (a TSDFMesh)")
     bases = {k: v for k, v in (("pix_base", pix_base), ("rel_base", rel_base)) if v is not None}
@@ -821,7 +823,7 @@ def reconstruct_scan(model, images, Ks, Es, depth_ranges, pairs, conf=0.9, thres
     refs = np.asarray(scan["ref_views"])
     res = fusion_mod.fuse_scene(scan["depth"], scan["photometric_confidence"], img, scan["Ks"][refs], scan["Es"][refs], fpairs,
                                 conf, thres_view, device=dev, method=fusion, voxel_size=voxel_size,
-                                voxel_reduce=voxel_reduce, outliers=outliers, normals=normals, mesh=mesh, **bases)
+                                voxel_reduce=voxel_reduce, outliers=outliers, normals=normals, mesh=mesh, mesh_clean=mesh_clean, **bases)
     res.scan = scan
     if plyfilename is not None:
         fusion_mod.write_scene_ply(plyfilename, res, thinned=voxel_size is not None)
