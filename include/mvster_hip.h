@@ -860,6 +860,60 @@ int mvster_mesh_emit_triangles(const float* tsdf, const int* weight, int nx, int
                                const unsigned char* edge_mask, const unsigned short* rank, const long* voffsets,
                                const long* toffsets, long Nv, long Nt, int* triangles, void* stream);
 
+/* ---- brick-sparse TSDF volumes (csrc/geo_mesh_sparse.hip, csrc/tsdf_sparse_math.h).  The virtual grid
+ * has nx x ny x nz nodes, each axis 2 .. 2^20 and no limit on the product; a brick is 8 x 8 x 8 nodes, brick (bi, bj, bk) has the
+ * number bi + nbx (bj + nby bk) with nb = ceil(n / 8), and the grid may hold at most 2^27 bricks.  A sparse volume is bricks [Nb]
+ * int32 (ascending brick numbers), brick_slot [nbricks] int32 (a brick's place in `bricks`, -1 = absent) and brick-major tsdf /
+ * weight / has_color [Nb, 512], rgb [Nb, 512, 3]; a node's place in its brick is li + 8 (lj + 8 lk).  It means the dense volume of
+ * the same grid with every node of an absent brick at weight 0, tsdf 1.  Every entry point validates before any HIP call; no
+ * atomics: two runs give the same bytes. ---- */
+
+/* The bricks of the virtual grid (the length of flags and brick_slot), or MVSTER_ERR_SHAPE where the grid is refused. */
+int mvster_tsdf_sparse_bricks(int nx, int ny, int nz);
+
+/* flags [nbricks] uint8 <- 1 for every brick that some pixel with mask != 0 and a finite depth > 0 allocates (its slab between
+ * z = max(d - trunc, 0) and d + trunc, back-projected, widened by 2 nodes; K_10 is taken as 0), 0 elsewhere.  depth / mask
+ * [V,H,W], views [V,21] as mvster_tsdf_integrate.  One memset and one launch. */
+int mvster_tsdf_sparse_mark(const float* depth, const unsigned char* mask, const double* views, int V, int H, int W, double ox,
+                            double oy, double oz, double voxel, int nx, int ny, int nz, double trunc, unsigned char* flags,
+                            void* stream);
+
+/* counts [ceil(nbricks / 512)] int32 (scratch) and offsets [that + 1] int64 = the exclusive scan of the flags set per tile of 512
+ * bricks; its last word is Nb, the caller's one read-back of an allocation.  Two launches. */
+int mvster_tsdf_sparse_compact_count(const unsigned char* flags, long nbricks, int* counts, long* offsets, void* stream);
+
+/* brick_slot [nbricks] and bricks [Nb] from the flags and the offsets of mvster_tsdf_sparse_compact_count.  Nb = 0 still writes
+ * brick_slot (all -1); bricks may then be NULL.  One launch. */
+int mvster_tsdf_sparse_compact_emit(const unsigned char* flags, long nbricks, const long* offsets, long Nb, int* brick_slot,
+                                    int* bricks, void* stream);
+
+/* All V views fused into the bricks [Nb] (any ascending set in range) in ONE launch, one workgroup per brick, with
+ * tsdf::add_view: the nodes carry exactly what mvster_tsdf_integrate gives them.  Words of a partial brick beyond the grid get
+ * weight 0, tsdf 1, rgb 0, has_color 0.  Nb = 0 launches nothing. */
+int mvster_tsdf_sparse_integrate(const float* depth, const unsigned char* mask, const unsigned char* images, const double* views,
+                                 int V, int H, int W, double ox, double oy, double oz, double voxel, int nx, int ny, int nz,
+                                 double trunc, const int* bricks, long Nb, float* tsdf, int* weight, unsigned char* rgb,
+                                 unsigned char* has_color, void* stream);
+
+/* The counting passes of a sparse extraction (min_weight >= 1, Nb >= 1): edge_mask [Nb,512] uint8, rank [Nb,512] uint16 = the
+ * vertices of the nodes before a node in its brick, vcounts / tcounts [Nb] int32 (scratch), voffsets / toffsets [Nb + 1] int64;
+ * their last words are Nv and Nt, the caller's one read-back.  Four launches. */
+int mvster_mesh_sparse_count(const float* tsdf, const int* weight, const int* brick_slot, const int* bricks, long Nb, int nx, int ny,
+                             int nz, int min_weight, unsigned char* edge_mask, unsigned short* rank, int* vcounts, int* tcounts,
+                             long* voffsets, long* toffsets, void* stream);
+
+/* vertices [Nv,3] float32, colors [Nv,3] uint8 and, where keys is not NULL, keys [Nv] int64 = global owner node * 8 + d, in the
+ * order (brick, local node, d).  Nv = 0 launches nothing; Nv above 2^31 - 1 is MVSTER_ERR_SHAPE.  One launch. */
+int mvster_mesh_sparse_emit_vertices(const float* tsdf, const int* weight, const unsigned char* rgb, const unsigned char* has_color,
+                                     const int* brick_slot, const int* bricks, long Nb, double ox, double oy, double oz, double voxel,
+                                     int nx, int ny, int nz, const unsigned char* edge_mask, const unsigned short* rank,
+                                     const long* voffsets, long Nv, float* vertices, unsigned char* colors, long* keys, void* stream);
+
+/* triangles [Nt,3] int32 in the order (brick, local cell, tetrahedron, triangle).  Nt = 0 launches nothing.  One launch. */
+int mvster_mesh_sparse_emit_triangles(const float* tsdf, const int* weight, const int* brick_slot, const int* bricks, long Nb, int nx,
+                                      int ny, int nz, int min_weight, const unsigned char* edge_mask, const unsigned short* rank,
+                                      const long* voffsets, const long* toffsets, long Nv, long Nt, int* triangles, void* stream);
+
 /* ---- cleaning a mesh: weld, components, compaction, vertex normals (csrc/geo_mesh_clean.hip, csrc/mesh_math.h; DESIGN.md
  * section 4.24).  A mesh is vertices [Nv,3] float32, triangles [Nt,3] int32 with every index in 0 .. Nv-1 (the caller checks
  * that; the kernels leave a triangle with another index out and never reach out of bounds), Nv and Nt at most 2^29. ---- */

@@ -128,6 +128,14 @@ SIGNATURES = {
     "mvster_mesh_count": [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f],
     "mvster_mesh_emit_vertices": [_f, _f, _f] + [ctypes.c_double] * 4 + [_i, _i, _i, _f, _f, _f, _l, _f, _f, _f],
     "mvster_mesh_emit_triangles": [_f, _f, _i, _i, _i, _i, _f, _f, _f, _f, _l, _l, _f, _f],
+    "mvster_tsdf_sparse_bricks": [_i, _i, _i],
+    "mvster_tsdf_sparse_mark": [_f, _f, _f, _i, _i, _i] + [ctypes.c_double] * 4 + [_i, _i, _i, ctypes.c_double, _f, _f],
+    "mvster_tsdf_sparse_compact_count": [_f, _l, _f, _f, _f],
+    "mvster_tsdf_sparse_compact_emit": [_f, _l, _f, _l, _f, _f, _f],
+    "mvster_tsdf_sparse_integrate": [_f, _f, _f, _f, _i, _i, _i] + [ctypes.c_double] * 4 + [_i, _i, _i, ctypes.c_double, _f, _l] + [_f] * 5,
+    "mvster_mesh_sparse_count": [_f, _f, _f, _f, _l, _i, _i, _i, _i] + [_f] * 7,
+    "mvster_mesh_sparse_emit_vertices": [_f] * 6 + [_l] + [ctypes.c_double] * 4 + [_i, _i, _i, _f, _f, _f, _l, _f, _f, _f, _f],
+    "mvster_mesh_sparse_emit_triangles": [_f, _f, _f, _f, _l, _i, _i, _i, _i, _f, _f, _f, _f, _l, _l, _f, _f],
     "mvster_mesh_clean_work": [_l, _l, _f, _f],
     "mvster_mesh_clean_plan": [_f, _f, _l, _l, _i, _l, _i, _f, _l] + [_f] * 7 + [_l, _f, _f, _f],
     "mvster_mesh_normals_blocks": [_l],

@@ -892,7 +892,8 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     ``normals``, ``final_normals`` / ``final_normal_valid``: oriented toward the camera centre -R^T T of the reference view a
     point came from (a voxel: of its first point).  Every other key stays byte-equal.
 
-    ``mesh`` (a ``TSDFMesh(voxel_size, trunc=None, min_weight=2)``; default None: nothing changes and no launch is added): the
+    ``mesh`` (a ``TSDFMesh(voxel_size, trunc=None, min_weight=2, sparse=False)``; default None: nothing changes and no launch is
+    added; ``sparse=True``: the same mesh from a brick-sparse volume, DESIGN.md section 4.25, in another vertex order): the
     reference views' ``depth_est_averaged`` (as float32) under ``final_mask``, their images and cameras are fused into a TSDF
     over the box of the cloud that would be written (``final_*``, else ``thin_*``, else ``points``) and meshed by marching
     tetrahedra (``mesh.mesh_scene``); the result additionally holds ``mesh_vertices`` [Nv,3] float32,
@@ -1012,7 +1013,7 @@ def fuse_scene(depths, confidences, images, Ks, Es, pairs, conf_thres, thres_vie
     if outliers is not None or normals is not None:
         res.update(_clean_scene(res, Es, pairs, voxel_size is not None, outliers, normals))
     if mesh_spec is not None:
-        res.update(mesh_mod.mesh_fused(res, img, Ks, Es, [r for r, _ in pairs], mesh_spec, clean=clean_spec))
+        res.update(mesh_mod.mesh_fused(res, img, Ks, Es, [r for r, _ in pairs], mesh_spec, clean=clean_spec, sparse=mesh.sparse))
     return res
 
 

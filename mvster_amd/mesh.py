@@ -23,8 +23,36 @@ MEMORY_BUDGET = 8 << 30                 # bytes a mesh_scene volume and its extr
 MIN_TRUNC_VOXELS = 2.0                  # trunc >= 2 voxels: the ends of a crossing edge (length <= sqrt(3) voxels) are not both clamped
 DEFAULT_TRUNC_VOXELS = 4.0
 
-TSDFMesh = collections.namedtuple("TSDFMesh", "voxel_size trunc min_weight", defaults=(None, 2))
+MAX_AXIS = 1 << 20                      # tsdfs::kMaxAxis: nodes per axis of a sparse volume's virtual grid
+MAX_BRICKS = 1 << 27                    # tsdfs::kMaxBricks: the brick directory is dense over the virtual grid
+BRICK = 8
+BRICK_NODES = BRICK ** 3
+BRICK_BYTES = BRICK_NODES * NODE_BYTES + 12      # a brick's nodes with their extraction + its counts and offsets
+DIRECTORY_BYTES = 5                     # per brick of the virtual grid: the directory word and the allocation's flag
+
+
+class TSDFMesh(collections.namedtuple("TSDFMesh", "voxel_size trunc min_weight", defaults=(None, 2))):
+    """The ``mesh=`` spec of the scan-level entry points.  ``sparse`` (default False) is a fourth field kept beside the tuple, so
+    that ``TSDFMesh(0.01) == (0.01, None, 2)`` stays true: with ``sparse=True`` the scan is meshed in a ``SparseTSDFVolume``."""
+    def __new__(cls, voxel_size, trunc=None, min_weight=2, sparse=False):
+        self = super().__new__(cls, voxel_size, trunc, min_weight)
+        self.sparse = sparse
+        return self
+
+    def __repr__(self):
+        return "TSDFMesh(voxel_size=%r, trunc=%r, min_weight=%r, sparse=%r)" % (tuple(self) + (self.sparse,))
+
+    def _replace(self, **kw):
+        d = dict(zip(self._fields, self), sparse=self.sparse)
+        d.update(kw)
+        return TSDFMesh(**d)
+
+    def __reduce__(self):
+        return TSDFMesh, tuple(self) + (self.sparse,)
+
+
 Mesh = collections.namedtuple("Mesh", "vertices colors triangles")
+SparseMesh = collections.namedtuple("SparseMesh", "vertices colors triangles vertex_key")
 # the ``mesh_clean=`` spec of the scan-level entry points (a keyword of its own: TSDFMesh(0.01) == (0.01, None, 2) is pinned)
 MeshClean = collections.namedtuple("MeshClean", "weld min_triangles largest_only normals", defaults=(True, 0, False, False))
 
@@ -106,6 +134,7 @@ def check_mesh_spec(what, mesh):
     if not isinstance(mesh, TSDFMesh):
         raise RuntimeError("%s: mesh must be None or a TSDFMesh, not %r" % (what, mesh))
     voxel = _number(what, "mesh.voxel_size", mesh.voxel_size)
+    _flag(what, "mesh.sparse", mesh.sparse)
     return voxel, _check_trunc(what, voxel, mesh.trunc), _check_min_weight(what, mesh.min_weight)
 
 
@@ -288,12 +317,301 @@ def extract_mesh(volume, min_weight=1, fill=None):
     return Mesh(vertices, colors, triangles)
 
 
+# ---- brick-sparse volumes (defined exactly in mvster_amd/csrc/tsdf_sparse_math.h) -------------------------------
+
+class SparseTSDFVolume:
+    """A TSDF stored in 8 x 8 x 8 bricks: the grid (``origin``, ``voxel_size``, ``dims`` = (nx, ny, nz), each axis at most 2^20 and
+    no limit on the product, ``trunc``), the directory ``brick_slot`` [nbz,nby,nbx] int32 (a brick's place in ``bricks``, -1 =
+    absent), ``bricks`` [Nb] int32 (ascending brick numbers bi + nbx (bj + nby bk)) and brick-major ``tsdf`` / ``weight`` /
+    ``has_color`` [Nb,512] and ``rgb`` [Nb,512,3], a node's place in its brick being li + 8 (lj + 8 lk).  It means the dense
+    ``TSDFVolume`` of the same grid with every node of an absent brick at weight 0, tsdf 1 (``densify``)."""
+
+    def __init__(self, brick_slot, bricks, tsdf, weight, rgb, has_color, origin, voxel_size, dims, trunc):
+        self.brick_slot, self.bricks = brick_slot, bricks
+        self.tsdf, self.weight, self.rgb, self.has_color = tsdf, weight, rgb, has_color
+        self.origin, self.voxel_size, self.dims, self.trunc = tuple(float(o) for o in origin), float(voxel_size), tuple(dims), trunc
+
+    @property
+    def n_bricks(self):
+        return int(self.bricks.shape[0])
+
+    def params(self):
+        return dict(origin=self.origin, voxel_size=self.voxel_size, dims=self.dims, trunc=self.trunc, sparse=True,
+                    bricks=self.n_bricks, grid_bricks=int(self.brick_slot.numel()))
+
+
+def brick_dims(dims):
+    """-> (nbx, nby, nbz), the bricks per axis of a grid of ``dims`` nodes"""
+    return tuple((int(n) + BRICK - 1) // BRICK for n in dims)
+
+
+def _check_sparse_dims(what, dims):
+    try:
+        d = tuple(int(x) for x in dims)
+        exact = all(int(x) == x for x in dims)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: dims must be three integers (nx, ny, nz), not %r" % (what, dims)) from None
+    if len(d) != 3 or not exact:
+        raise RuntimeError("%s: dims must be three integers (nx, ny, nz), not %r" % (what, dims))
+    if min(d) < 2 or max(d) > MAX_AXIS:
+        raise RuntimeError("%s: a sparse grid needs 2 .. 2^20 nodes per axis, not %r" % (what, d))
+    nb = brick_dims(d)
+    if nb[0] * nb[1] * nb[2] > MAX_BRICKS:
+        raise RuntimeError("%s: a sparse grid holds at most 2^27 bricks of 8 x 8 x 8 nodes (its directory is dense), not %d (%r nodes)" %
+                           (what, nb[0] * nb[1] * nb[2], d))
+    return d, nb
+
+
+def _check_allocation_cameras(what, views, origin, voxel, dims):
+    """What the covering property of ``allocate`` assumes of the cameras (tsdf_sparse_math.h): K upper triangular with a
+    diagonal that is not 0, and R orthonormal closely enough that R^T (R x) stays within a quarter of a voxel of every node x."""
+    reach = max(max(abs(o), abs(o + voxel * (n - 1))) for o, n in zip(origin, dims))
+    for v, row in enumerate(views):
+        K, R = row[:9].reshape(3, 3), row[9:18].reshape(3, 3)
+        if K[1, 0] != 0.0 or K[0, 0] == 0.0 or K[1, 1] == 0.0:
+            raise RuntimeError("%s: Ks[%d] must be upper triangular with K_00 and K_11 not 0 (the allocation inverts it in closed "
+                               "form), not %r" % (what, v, K.tolist()))
+        err = float(np.abs(R.T @ R - np.eye(3)).max())
+        if 3.0 * err * reach > 0.25 * voxel:
+            raise RuntimeError("%s: the rotation of view %d is orthonormal only to %.3g; at a distance of %g from the world's origin "
+                               "that moves a node by more than a quarter of the voxel %g, and the allocation could miss a brick" %
+                               (what, v, err, reach, voxel))
+
+
+def _mask_bytes(masks, V, H, W, dev):
+    return torch.ones(V, H, W, device=dev, dtype=torch.uint8) if masks is None else _stack(masks, dev, torch.bool).to(torch.uint8)
+
+
+def _allocate(what, depth, mask, views, o, voxel, dims, nb, t, dev):
+    """-> brick_slot [nbz,nby,nbx] int32 and bricks [Nb] int32 on ``dev`` (one read-back: Nb)"""
+    lib = _lib.load()
+    V, H, W = depth.shape
+    nbricks = nb[0] * nb[1] * nb[2]
+    tiles = (nbricks + BRICK_NODES - 1) // BRICK_NODES
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        table = torch.from_numpy(views).to(dev)
+        flags = torch.empty(nbricks, device=dev, dtype=torch.uint8)
+        counts = torch.empty(tiles, device=dev, dtype=torch.int32)
+        offsets = torch.empty(tiles + 1, device=dev, dtype=torch.int64)
+        _lib.check(lib.mvster_tsdf_sparse_mark(depth.data_ptr(), mask.data_ptr(), table.data_ptr(), V, H, W, o[0], o[1], o[2], voxel,
+                                               dims[0], dims[1], dims[2], t, flags.data_ptr(), stream), "tsdf_sparse_mark")
+        _lib.check(lib.mvster_tsdf_sparse_compact_count(flags.data_ptr(), nbricks, counts.data_ptr(), offsets.data_ptr(), stream),
+                   "tsdf_sparse_compact_count")
+        n = int(offsets[tiles].cpu())                                             # the one read-back
+        slot = torch.empty(nb[2], nb[1], nb[0], device=dev, dtype=torch.int32)
+        bricks = torch.empty(n, device=dev, dtype=torch.int32)
+        _lib.check(lib.mvster_tsdf_sparse_compact_emit(flags.data_ptr(), nbricks, offsets.data_ptr(), n, slot.data_ptr(),
+                                                       bricks.data_ptr() if n else None, stream), "tsdf_sparse_compact_emit")
+    return slot, bricks
+
+
+def allocate_bricks(depths, masks, Ks, Es, origin, voxel_size, dims, trunc, device=None):
+    """The bricks of a sparse volume that the maps of a scan need, on the GPU (``mvster_tsdf_sparse_mark`` and the two compaction
+    calls): every pixel with mask != 0 and a finite depth d > 0 allocates the bricks its slab touches -- its frustum between camera
+    z = max(d - trunc, 0) and d + trunc, back-projected, as a box in node coordinates widened by 2 nodes.  Every node some view
+    counts within +-trunc then lies with its 26 neighbours in allocated bricks (proved in tsdf_sparse_math.h), so the sparse mesh
+    is the dense one.  K must be upper triangular.  -> (``brick_slot`` [nbz,nby,nbx] int32, ``bricks`` [Nb] int32 ascending).  One
+    read-back (Nb).  No CPU fallback."""
+    what = "allocate_bricks"
+    ds = _shape(depths)
+    if len(ds) != 3 or min(ds) < 1 or max(ds[1:]) > MAX_SIDE:
+        raise RuntimeError("%s: depths must be [V,H,W] with V, H, W >= 1 and H, W <= 2^20, not %s" % (what, ds))
+    if masks is not None and _shape(masks) != ds:
+        raise RuntimeError("%s: masks must have the shape of depths %s, not %s" % (what, ds, _shape(masks)))
+    V, H, W = ds
+    views = _cameras(what, Ks, Es, V)
+    o = _check_origin(what, origin)
+    voxel = _number(what, "voxel_size", voxel_size)
+    d, nb = _check_sparse_dims(what, dims)
+    t = _number(what, "trunc", trunc)
+    _check_allocation_cameras(what, views, o, voxel, d)
+    dev = _device(what, device, (depths, masks))
+    return _allocate(what, _stack(depths, dev, torch.float32), _mask_bytes(masks, V, H, W, dev), views, o, voxel, d, nb, t, dev)
+
+
+def _check_bricks(what, bricks, nbricks, dev):
+    """A caller's own brick list: integers, ascending without duplicates, in 0 .. nbricks - 1 -> int32 tensor on ``dev``"""
+    b = bricks.detach().cpu().numpy() if isinstance(bricks, torch.Tensor) else np.asarray(bricks)
+    if b.ndim != 1 or (b.size and b.dtype.kind not in "iu"):
+        raise RuntimeError("%s: bricks must be a 1-d array of integer brick numbers, not %s %s" % (what, b.shape, b.dtype))
+    b = b.astype(np.int64)
+    if b.size and (b.min() < 0 or b.max() >= nbricks):
+        raise RuntimeError("%s: bricks must lie in 0 .. %d, not %d" % (what, nbricks - 1, b.min() if b.min() < 0 else b.max()))
+    if b.size > 1 and not (np.diff(b) > 0).all():
+        raise RuntimeError("%s: bricks must be ascending and without duplicates" % what)
+    return torch.from_numpy(b.astype(np.int32)).to(dev)
+
+
+def sparse_bytes(n_bricks, grid_bricks):
+    """The bytes a sparse volume of ``n_bricks`` bricks and its extraction take in a virtual grid of ``grid_bricks`` bricks"""
+    return int(n_bricks) * BRICK_BYTES + int(grid_bricks) * DIRECTORY_BYTES
+
+
+def integrate_tsdf_sparse(depths, masks, images, Ks, Es, origin, voxel_size, dims, trunc, bricks=None, device=None, fill=None,
+                          memory_budget=None):
+    """``integrate_tsdf`` into a ``SparseTSDFVolume`` (``mvster_tsdf_sparse_integrate``: one launch for all views, one workgroup
+    per brick, the same ``tsdf::add_view``): the nodes of allocated bricks carry exactly what ``integrate_tsdf`` gives them.
+    ``dims``: each axis 2 .. 2^20, at most 2^27 bricks in all, no limit on the nodes.  ``bricks`` (None: ``allocate_bricks`` of the
+    same maps): the caller's own set of brick numbers, ascending, without duplicates, in range.  ``memory_budget`` (None: not
+    checked): refused where the allocated bricks with their extraction take more bytes, after the allocation's read-back.
+    ``fill`` (tests): a byte the outputs are filled with before the kernel writes them.  No CPU fallback."""
+    what = "integrate_tsdf_sparse"
+    V, H, W = _check_maps(what, depths, masks, images)
+    views = _cameras(what, Ks, Es, V)
+    o = _check_origin(what, origin)
+    voxel = _number(what, "voxel_size", voxel_size)
+    d, nb = _check_sparse_dims(what, dims)
+    t = _number(what, "trunc", trunc)
+    budget = None if memory_budget is None else _number(what, "memory_budget", memory_budget)
+    nbricks = nb[0] * nb[1] * nb[2]
+    if bricks is None:
+        _check_allocation_cameras(what, views, o, voxel, d)
+    dev = _device(what, device, (depths, masks, images))
+    if bricks is not None:
+        bricks = _check_bricks(what, bricks, nbricks, dev)
+    depth = _stack(depths, dev, torch.float32)
+    mask = _mask_bytes(masks, V, H, W, dev)
+    img = _stack(images, dev, torch.uint8)
+    if bricks is None:
+        slot, bricks = _allocate(what, depth, mask, views, o, voxel, d, nb, t, dev)
+    else:
+        slot = torch.full((nbricks,), -1, device=dev, dtype=torch.int32)
+        slot[bricks.long()] = torch.arange(len(bricks), device=dev, dtype=torch.int32)
+        slot = slot.view(nb[2], nb[1], nb[0])
+    n = int(bricks.shape[0])
+    if budget is not None and sparse_bytes(n, nbricks) > budget:
+        # the bricks follow a surface: their number falls with the square of the voxel size (the directory's with the cube)
+        fit = voxel * 1.05 * math.sqrt(sparse_bytes(n, nbricks) / budget)
+        raise RuntimeError("%s: the volume would hold %d bricks of 8 x 8 x 8 nodes (of %d in the grid) = %d bytes with its extraction, "
+                           "above the memory_budget of %d bytes; a voxel_size of about %g would fit" %
+                           (what, n, nbricks, sparse_bytes(n, nbricks), int(budget), fit))
+    vol = SparseTSDFVolume(slot, bricks, torch.empty(n, BRICK_NODES, device=dev, dtype=torch.float32),
+                           torch.empty(n, BRICK_NODES, device=dev, dtype=torch.int32),
+                           torch.empty(n, BRICK_NODES, 3, device=dev, dtype=torch.uint8),
+                           torch.empty(n, BRICK_NODES, device=dev, dtype=torch.uint8), o, voxel, d, t)
+    if fill is not None:
+        for out in (vol.tsdf, vol.weight, vol.rgb, vol.has_color):
+            out.view(torch.uint8).fill_(int(fill))
+    if n:
+        with torch.cuda.device(dev):
+            table = torch.from_numpy(views).to(dev)
+            rc = _lib.load().mvster_tsdf_sparse_integrate(depth.data_ptr(), mask.data_ptr(), img.data_ptr(), table.data_ptr(), V, H, W,
+                                                          o[0], o[1], o[2], voxel, d[0], d[1], d[2], t, bricks.data_ptr(), n,
+                                                          vol.tsdf.data_ptr(), vol.weight.data_ptr(), vol.rgb.data_ptr(),
+                                                          vol.has_color.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(rc, "tsdf_sparse_integrate")
+    return vol
+
+
+def _check_sparse_volume(what, volume):
+    if not isinstance(volume, SparseTSDFVolume):
+        raise RuntimeError("%s: volume must be a SparseTSDFVolume, not %s" % (what, type(volume).__name__))
+    d, nb = _check_sparse_dims(what, volume.dims)
+    _check_origin(what, volume.origin)
+    _number(what, "volume.voxel_size", volume.voxel_size)
+    if not isinstance(volume.bricks, torch.Tensor) or volume.bricks.dim() != 1 or volume.bricks.dtype != torch.int32:
+        raise RuntimeError("%s: volume.bricks must be an int32 tensor [Nb]" % what)
+    n = volume.bricks.shape[0]
+    if n > nb[0] * nb[1] * nb[2]:
+        raise RuntimeError("%s: volume.bricks holds %d bricks, the grid %d" % (what, n, nb[0] * nb[1] * nb[2]))
+    for name, shape, dtype in (("brick_slot", (nb[2], nb[1], nb[0]), torch.int32), ("tsdf", (n, BRICK_NODES), torch.float32),
+                               ("weight", (n, BRICK_NODES), torch.int32), ("rgb", (n, BRICK_NODES, 3), torch.uint8),
+                               ("has_color", (n, BRICK_NODES), torch.uint8)):
+        t = getattr(volume, name)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype:
+            raise RuntimeError("%s: volume.%s must be a %s tensor of shape %s" % (what, name, dtype, shape))
+    for name in ("brick_slot", "bricks", "tsdf", "weight", "rgb", "has_color"):
+        t = getattr(volume, name)
+        if not t.is_cuda or t.device != volume.tsdf.device:
+            raise RuntimeError("%s: volume.%s must be on the GPU of volume.tsdf (there is no CPU fallback)" % (what, name))
+    return d, nb, n
+
+
+def extract_mesh_sparse(volume, min_weight=1, keys=False, fill=None):
+    """``extract_mesh`` of a ``SparseTSDFVolume`` on the GPU (``mvster_mesh_sparse_count`` / ``_emit_vertices`` /
+    ``_emit_triangles``): the dense extraction of the volume it means, a brick at a time on a 10 x 10 x 10 window staged in LDS.
+    -> ``Mesh``, or with ``keys`` a ``SparseMesh`` whose ``vertex_key`` [Nv] int64 = global owner node * 8 + d names every vertex
+    whatever the order.  Vertices are in the order (brick, node in the brick, d), triangles in (brick, cell, tetrahedron,
+    triangle): the same vertices and triangles as ``extract_mesh`` on ``densify(volume)``, in another order.  One read-back (the
+    two counts).  ``fill`` (tests): a byte the outputs are filled with before the kernels write them.  No CPU fallback."""
+    what = "extract_mesh_sparse"
+    mw = _check_min_weight(what, min_weight)
+    keys = _flag(what, "keys", keys)
+    (nx, ny, nz), nb, n = _check_sparse_volume(what, volume)
+    dev = volume.tsdf.device
+    tsdf, weight, rgb, has, slot, bricks = (getattr(volume, k).contiguous() for k in ("tsdf", "weight", "rgb", "has_color", "brick_slot",
+                                                                                     "bricks"))
+    nv = nt = 0
+    o, voxel = volume.origin, volume.voxel_size
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if n:
+            edge_mask = torch.empty(n * BRICK_NODES, device=dev, dtype=torch.uint8)
+            rank = torch.empty(n * BRICK_NODES, device=dev, dtype=torch.int16)
+            counts = torch.empty(2, n, device=dev, dtype=torch.int32)
+            offsets = torch.empty(2, n + 1, device=dev, dtype=torch.int64)
+            _lib.check(lib.mvster_mesh_sparse_count(tsdf.data_ptr(), weight.data_ptr(), slot.data_ptr(), bricks.data_ptr(), n, nx, ny, nz,
+                                                    mw, edge_mask.data_ptr(), rank.data_ptr(), counts[0].data_ptr(),
+                                                    counts[1].data_ptr(), offsets[0].data_ptr(), offsets[1].data_ptr(), stream),
+                       "mesh_sparse_count")
+            nv, nt = (int(c) for c in offsets[:, n].cpu())                        # the one read-back
+            if nv > MAX_NODES:
+                raise RuntimeError("extract_mesh_sparse: the mesh would have %d vertices; triangles hold int32 vertex numbers (at most "
+                                   "2^31 - 1)" % nv)
+        vertices = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+        colors = torch.empty(nv, 3, device=dev, dtype=torch.uint8)
+        triangles = torch.empty(nt, 3, device=dev, dtype=torch.int32)
+        vkeys = torch.empty(nv, device=dev, dtype=torch.int64) if keys else None
+        if fill is not None:
+            for t in (vertices, colors, triangles) + ((vkeys,) if keys else ()):
+                t.view(torch.uint8).fill_(int(fill))
+        if nv:
+            _lib.check(lib.mvster_mesh_sparse_emit_vertices(tsdf.data_ptr(), weight.data_ptr(), rgb.data_ptr(), has.data_ptr(),
+                                                            slot.data_ptr(), bricks.data_ptr(), n, o[0], o[1], o[2], voxel, nx, ny, nz,
+                                                            edge_mask.data_ptr(), rank.data_ptr(), offsets[0].data_ptr(), nv,
+                                                            vertices.data_ptr(), colors.data_ptr(), vkeys.data_ptr() if keys else None,
+                                                            stream), "mesh_sparse_emit_vertices")
+        if nt:
+            _lib.check(lib.mvster_mesh_sparse_emit_triangles(tsdf.data_ptr(), weight.data_ptr(), slot.data_ptr(), bricks.data_ptr(), n,
+                                                             nx, ny, nz, mw, edge_mask.data_ptr(), rank.data_ptr(),
+                                                             offsets[0].data_ptr(), offsets[1].data_ptr(), nv, nt, triangles.data_ptr(),
+                                                             stream), "mesh_sparse_emit_triangles")
+    return SparseMesh(vertices, colors, triangles, vkeys) if keys else Mesh(vertices, colors, triangles)
+
+
+def densify(volume):
+    """The dense ``TSDFVolume`` a ``SparseTSDFVolume`` means (plain torch scatter; for tests and small grids): nodes of absent
+    bricks get weight 0, tsdf 1, rgb 0, has_color 0.  Refused above the dense limits."""
+    what = "densify"
+    (nx, ny, nz), nb, n = _check_sparse_volume(what, volume)
+    _check_dims(what, (nx, ny, nz))
+    dev = volume.tsdf.device
+    px, py, pz = (b * BRICK for b in nb)                                          # the grid padded to whole bricks
+    full = dict(tsdf=torch.ones(pz, py, px, device=dev, dtype=torch.float32), weight=torch.zeros(pz, py, px, device=dev, dtype=torch.int32),
+                rgb=torch.zeros(pz, py, px, 3, device=dev, dtype=torch.uint8), has_color=torch.zeros(pz, py, px, device=dev, dtype=torch.uint8))
+    b = volume.bricks.long()
+    bi, bj, bk = b % nb[0], (b // nb[0]) % nb[1], b // (nb[0] * nb[1])
+    l = torch.arange(BRICK, device=dev)
+    k = (bk[:, None] * BRICK + l)[:, :, None, None]
+    j = (bj[:, None] * BRICK + l)[:, None, :, None]
+    i = (bi[:, None] * BRICK + l)[:, None, None, :]
+    for name, t in full.items():
+        src = getattr(volume, name)
+        t[k, j, i] = src.view((n, BRICK, BRICK, BRICK) + tuple(src.shape[2:]))
+    return TSDFVolume(*(full[name][:nz, :ny, :nx].contiguous() for name in ("tsdf", "weight", "rgb", "has_color")), volume.origin,
+                      volume.voxel_size, (nx, ny, nz), volume.trunc)
+
+
 # ---- a scan's maps to a mesh ------------------------------------------------------------------------------------------------------------
 
-def grid_for_bounds(what, lo, hi, voxel, trunc, memory_budget=MEMORY_BUDGET):
+def grid_for_bounds(what, lo, hi, voxel, trunc, memory_budget=MEMORY_BUDGET, sparse=False):
     """The grid of ``mesh_scene``: the box (lo, hi) padded by ``trunc`` on every side, origin at its low corner, as many nodes
     per axis as cover it (at least 2) -> (origin, dims).  Refused where the volume and its extraction (``NODE_BYTES`` a node)
-    would take more than ``memory_budget`` bytes or more than 2^31 - 1 nodes; the message names the voxel size that fits."""
+    would take more than ``memory_budget`` bytes or more than 2^31 - 1 nodes; the message names the voxel size that fits.
+    ``sparse``: the virtual grid of a ``SparseTSDFVolume``: the node cap does not apply; refused above 2^20 nodes per axis, 2^27
+    bricks, or where the brick directory alone is above the budget (the bricks are checked once they are allocated)."""
     lo, hi = _check_origin(what, lo), _check_origin(what, hi)
     if any(h < l for l, h in zip(lo, hi)):
         raise RuntimeError("%s: bounds must be (lo, hi) with lo <= hi on every axis, not %r, %r" % (what, lo, hi))
@@ -301,6 +619,14 @@ def grid_for_bounds(what, lo, hi, voxel, trunc, memory_budget=MEMORY_BUDGET):
     origin = tuple(l - trunc for l in lo)
     ext = [(h + trunc) - o for h, o in zip(hi, origin)]
     dims = tuple(max(2, int(math.ceil(e / voxel)) + 1) for e in ext)
+    if sparse:
+        nb = brick_dims(dims)
+        grid_bricks = nb[0] * nb[1] * nb[2]
+        if max(dims) > MAX_AXIS or grid_bricks > MAX_BRICKS or grid_bricks * DIRECTORY_BYTES > budget:
+            raise RuntimeError("%s: the sparse grid would hold %d x %d x %d nodes in %d bricks (a directory of %d bytes), above 2^20 "
+                               "nodes per axis, 2^27 bricks or the memory_budget of %d bytes" %
+                               (what, dims[0], dims[1], dims[2], grid_bricks, grid_bricks * DIRECTORY_BYTES, int(budget)))
+        return origin, dims
     nodes = dims[0] * dims[1] * dims[2]
     cap = min(MAX_NODES, int(budget // NODE_BYTES))
     if nodes > cap:
@@ -339,7 +665,7 @@ def _frustum_bounds(depth, mask, views, H, W):
 
 
 def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=None, min_weight=2, memory_budget=MEMORY_BUDGET,
-               device=None, fill=None, mesh_clean=None):
+               device=None, fill=None, mesh_clean=None, sparse=False):
     """``integrate_tsdf`` then ``extract_mesh`` for the maps of a scan.  ``trunc`` defaults to 4 ``voxel_size`` and is refused
     below 2 ``voxel_size`` (the ends of a crossing edge could both be clamped).  ``bounds`` = (lo, hi), three numbers each: the
     grid covers the box padded by ``trunc``, its origin is lo - trunc (``grid_for_bounds``); None: the box of the views' frusta
@@ -347,8 +673,13 @@ def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=Non
     with the voxel size that would fit.  ``min_weight`` (default 2): a node seen by fewer views is unknown.  -> dict:
     ``vertices``, ``colors``, ``triangles`` (as ``extract_mesh``) and ``volume`` (the ``TSDFVolume``).  ``mesh_clean`` (a
     ``MeshClean``; default None: nothing changes and no launch is added): the extracted mesh goes through ``clean_mesh`` and
-    the three keys hold the cleaned mesh, with ``clean_stats`` and, where asked for, ``normals`` / ``normals_valid``."""
+    the three keys hold the cleaned mesh, with ``clean_stats`` and, where asked for, ``normals`` / ``normals_valid``.
+    ``sparse`` (default False: nothing changes, the same launches and bytes): ``allocate_bricks``, ``integrate_tsdf_sparse`` and
+    ``extract_mesh_sparse``: the node cap of the dense grid does not apply, ``memory_budget`` is checked
+    against the allocated bricks, ``volume`` is a ``SparseTSDFVolume`` and the result also holds ``vertex_key``.  The mesh is
+    the dense one in another vertex and triangle order."""
     what = "mesh_scene"
+    sparse = _flag(what, "sparse", sparse)
     clean = check_clean_spec(what, mesh_clean)
     V, H, W = _check_maps(what, depths, masks, images)
     views = _cameras(what, Ks, Es, V)
@@ -360,7 +691,7 @@ def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=Non
             lo, hi = bounds
         except (TypeError, ValueError):
             raise RuntimeError("%s: bounds must be (lo, hi), not %r" % (what, bounds)) from None
-        origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget)
+        origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget, sparse)
     else:
         _number(what, "memory_budget", memory_budget)
     dev = _device(what, device, (depths, masks, images))
@@ -368,12 +699,20 @@ def mesh_scene(depths, masks, images, Ks, Es, voxel_size, trunc=None, bounds=Non
     mask = torch.ones(V, H, W, device=dev, dtype=torch.uint8) if masks is None else _stack(masks, dev, torch.bool).to(torch.uint8)
     if bounds is None:
         lo, hi = _frustum_bounds(depth, mask, views, H, W)
-        origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget)
-    vol = integrate_tsdf(depth, mask, images, Ks, Es, origin, voxel, dims, t, device=dev)
-    m = extract_mesh(vol, mw, fill=fill)
-    out = dict(vertices=m.vertices, colors=m.colors, triangles=m.triangles, volume=vol)
+        origin, dims = grid_for_bounds(what, lo, hi, voxel, t, memory_budget, sparse)
+    if sparse:
+        vol = integrate_tsdf_sparse(depth, mask, images, Ks, Es, origin, voxel, dims, t, device=dev, memory_budget=memory_budget)
+        m = extract_mesh_sparse(vol, mw, keys=True, fill=fill)
+        out = dict(vertices=m.vertices, colors=m.colors, triangles=m.triangles, volume=vol, vertex_key=m.vertex_key)
+    else:
+        vol = integrate_tsdf(depth, mask, images, Ks, Es, origin, voxel, dims, t, device=dev)
+        m = extract_mesh(vol, mw, fill=fill)
+        out = dict(vertices=m.vertices, colors=m.colors, triangles=m.triangles, volume=vol)
     if clean is not None:
-        out.update(_cleaned_keys(clean_mesh(m.vertices, m.triangles, m.colors, *clean, fill=fill, _checked=True), clean, ""))
+        c = clean_mesh(m.vertices, m.triangles, m.colors, *clean, fill=fill, _checked=True)
+        out.update(_cleaned_keys(c, clean, ""))
+        if sparse:
+            out["vertex_key"] = m.vertex_key[c["vertex_index"]]
     return out
 
 
@@ -386,12 +725,13 @@ def _cleaned_keys(c, clean, prefix):
     return out
 
 
-def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene", clean=None):
+def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene", clean=None, sparse=False):
     """fuse_scene's last step with a ``TSDFMesh``: the reference views' ``depth_est_averaged`` (as float32) under
     ``final_mask``, their images and cameras through ``mesh_scene``, within the box of the cloud that would be written
     (``final_*``, else ``thin_*``, else ``points``) -> the ``mesh_*`` keys.  An empty cloud gives an empty mesh.  ``clean`` (a
     checked ``MeshClean``): the mesh goes through ``clean_mesh``; the ``mesh_*`` keys hold the cleaned mesh, with
-    ``mesh_clean_stats`` and, where asked for, ``mesh_normals`` / ``mesh_normals_valid``."""
+    ``mesh_clean_stats`` and, where asked for, ``mesh_normals`` / ``mesh_normals_valid``.  ``sparse``: the spec's fourth field
+    (``mesh_scene(..., sparse=True)``; one more key, ``mesh_vertex_key``)."""
     voxel, trunc, mw = spec
     pts = res["final_points"] if "final_points" in res else res["thin_points"] if "thin_points" in res else res["points"]
     dev = pts.device
@@ -402,6 +742,8 @@ def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene", clean=No
         out = dict(mesh_vertices=torch.empty(0, 3, device=dev, dtype=torch.float32),
                    mesh_colors=torch.empty(0, 3, device=dev, dtype=torch.uint8),
                    mesh_triangles=torch.empty(0, 3, device=dev, dtype=torch.int32), mesh_volume=None)
+        if sparse:
+            out["mesh_vertex_key"] = torch.empty(0, device=dev, dtype=torch.int64)
         if clean is not None:
             out.update(_cleaned_keys(clean_mesh(out["mesh_vertices"], out["mesh_triangles"], out["mesh_colors"], *clean, _checked=True),
                                      clean, "mesh_"))
@@ -410,12 +752,17 @@ def mesh_fused(res, images, Ks, Es, ref_views, spec, what="fuse_scene", clean=No
     if not np.isfinite(box).all():
         raise RuntimeError("%s: the cloud holds a point that is not finite, so the mesh has no bounds" % what)
     m = mesh_scene(res["depth_est_averaged"].to(torch.float32), res["final_mask"], images[idx], [Ks[int(r)] for r in ref_views],
-                   [Es[int(r)] for r in ref_views], voxel, trunc, (box[0], box[1]), mw, device=dev)
+                   [Es[int(r)] for r in ref_views], voxel, trunc, (box[0], box[1]), mw, device=dev, **(dict(sparse=True) if sparse else {}))
     vol = m["volume"]
     out = dict(mesh_vertices=m["vertices"], mesh_colors=m["colors"], mesh_triangles=m["triangles"],
                mesh_volume=dict(vol.params(), min_weight=mw, bounds=(tuple(box[0]), tuple(box[1]))))
+    if sparse:
+        out["mesh_vertex_key"] = m["vertex_key"]
     if clean is not None:
-        out.update(_cleaned_keys(clean_mesh(m["vertices"], m["triangles"], m["colors"], *clean, _checked=True), clean, "mesh_"))
+        c = clean_mesh(m["vertices"], m["triangles"], m["colors"], *clean, _checked=True)
+        out.update(_cleaned_keys(c, clean, "mesh_"))
+        if sparse:
+            out["mesh_vertex_key"] = m["vertex_key"][c["vertex_index"]]
     return out
 
 
