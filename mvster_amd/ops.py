@@ -864,8 +864,15 @@ def _ticket(dev):
     return hit[0].data_ptr() + 16 * hit[1]
 
 
+def _bn_groups(name, x, groups):
+    """``groups`` equal slices along dim 0: anything else would leave the trailing rows out of the statistics and unwritten"""
+    if groups < 1 or x.dim() < 2 or x.shape[0] % groups != 0:
+        raise RuntimeError("%s: groups = %d does not divide the leading dimension of x %s" % (name, groups, tuple(x.shape)))
+
+
 def _bn_train_args(name, x, groups, *others):
     """The checks ``bn_train_fwd`` and ``bn_train_bwd`` share -> (C, rows per group, a fresh slot buffer)."""
+    _bn_groups(name, x, groups)
     _chk(x, name + ":x")
     for t, n in others:
         _chk(t, "%s:%s" % (name, n))
@@ -910,6 +917,7 @@ def bn_relu_fwd(x, scale, shift, relu, groups=1, skip=None):
     """y = relu(x*scale + shift) (+ skip) on a channels-last tensor [groups*n, ..., C] (training-mode BatchNorm apply);
     scale and shift are [groups, C]: each of the `groups` equal slices along dim 0 has its own statistics; ``skip`` is
     an optional tensor of x's shape added after the activation (the U-Net's skip connections)."""
+    _bn_groups("bn_relu_fwd", x, groups)
     _chk(x, "bn_relu_fwd:x")
     C = x.shape[-1]
     if skip is not None:
@@ -929,6 +937,7 @@ def bn_relu_bwd(x, gy, scale, shift, mean, rstd, relu, groups=1):
     training graph: the running statistics) -> (dx = g * scale, dbeta [C] = sum g, dgamma [C] = sum g*xh) with g =
     gy*(y>0), xh = (x-mean)*rstd; the parameter gradients are summed over the groups.  The backward through batch
     statistics is ``bn_train_bwd``."""
+    _bn_groups("bn_relu_bwd", x, groups)
     _chk(x, "bn_relu_bwd:x")
     _chk(gy, "bn_relu_bwd:gy")
     C = x.shape[-1]

@@ -506,6 +506,8 @@ def batch_norm_cl(x, bn, relu=False, groups=1, skip=None):
     statistics one after the other, exactly as ``groups`` separate calls of the module would (the reference runs its
     FPN once per view).  ``skip``: a tensor of x's shape added after the activation, in the same kernel (the U-Net's skip
     connections).  Gradients flow to x, gamma, beta (and skip).  Configurations the kernels do not cover raise."""
+    if groups < 1 or x.dim() < 2 or x.shape[0] % groups != 0:
+        raise RuntimeError("batch_norm_cl: groups = %d does not divide the leading dimension of x %s" % (groups, tuple(x.shape)))
     C = x.shape[-1]
     if not x.is_cuda:
         raise RuntimeError("batch_norm_cl: expected a GPU tensor (the HIP path has no CPU fallback)")
